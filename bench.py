@@ -18,10 +18,23 @@ while the next chunk is projected: ``rayen_amd.dist.ShardedStep``) leaves every 
 every rank.  ``value`` is that step; the same line carries ``no_gather`` (the projection
 alone, what a data-parallel training step needs).  ``--no-gather`` times only the latter.
 
-One JSON line on rank 0: metric / value (whole-job projections/s) plus ``roofline``
-(dominant kernel, live HIP-event timing on the launch stream, PMC traffic from the
-committed rocprofv3 summary of the same command) and ``cpu_baseline`` (the PyTorch-CPU
-oracle, same workload, timed on this box's host cores).
+One JSON line on rank 0: metric / value (whole-job projections/s), ``ms_per_step``, the
+feasibility of the outputs and ``roofline`` (dominant kernel, live HIP-event timing on the
+launch stream, PMC traffic from the committed rocprofv3 summary of the same command).  A
+plain run does only that: set up, settle, time the K steps, print the line.
+
+``--full`` adds everything measured beside the headline, each in runs of its own: the
+``cpu_baseline`` (the PyTorch-CPU oracle, same workload, timed on the host cores), the
+other fp32 families, the training step, the module behind its mapper, the inward-bias
+sweep, the L3-resident pair, the per-family violation report and, for N > 1, rank 0
+alone, the per-chunk trace and the all-gather alone (``--no-cpu-baseline`` and
+``--no-families`` still drop legs of it).
+
+``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/y.npy`` (rows x k,
+the run's dtype; with the all-gather, the gathered rows of every rank): every row where the
+output is at most DUMP_MAX_BYTES, else a fixed sample of rows (``torch.randperm`` seeded
+with 0, in ascending order).  The inputs are seeded, and the timed loop starts its
+rotation at the first batch, so the same arguments give the same inputs every run.
 """
 from __future__ import annotations
 
@@ -53,6 +66,8 @@ SETTLE_LAUNCHES = 150      # untimed launches of a comparison family before its 
 SETTLE_TOL = 0.02
 SETTLE_MIN_S = float(os.environ.get("RAYEN_BENCH_SETTLE_MIN_S", "0.25"))
 SETTLE_MAX_S = float(os.environ.get("RAYEN_BENCH_SETTLE_MAX_S", "2.0"))
+SETTLE_WINDOW_MAX_STEPS = 2000   # a settle window is W + K steps, each of the two capped here (a long timed run is its own settle)
+DUMP_MAX_BYTES = 32 << 20        # --dump-outputs: outputs above this are written as a seeded sample of their rows
 XGMI_GBPS_PER_LINK_PER_DIRECTION = 76.8   # MI355X: 7 links x 153.6 GB/s bidirectional per GPU, one direct link per peer
 BACKEND = os.environ.get("RAYEN_BENCH_BACKEND", "nccl")   # "gloo": CPU dry run of exactly this entry (tests/test_dist_gloo.py)
 
@@ -89,6 +104,11 @@ def parse(argv=None):
                     help="put the module's nn.Linear(D, n) mapper in front (create_map=True); 0 = identity mapper")
     ap.add_argument("--no-fuse", action="store_true", help="with --mapper: run the mapper as its own GEMM")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (CPU baseline, other fp32 families, training step, "
+                         "mapper, inward bias, L3-resident pair, violation report; N>1: solo rank, gather trace and alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/y.npy (a seeded sample of rows above 32 MiB)")
     return ap.parse_args(argv)
 
 
@@ -101,6 +121,7 @@ def cpu_baseline(raw, cs, B, dtype, budget_s, rng=1.0):
     """Reference op sequence (oracle/rayen_oracle.py) on the host cores, bounded sample of the workload."""
     from oracle import rayen_oracle as oracle
     cores = os.cpu_count() or 1
+    allowed = int(os.environ.get("OMP_NUM_THREADS") or cores)     # (a host that grants fewer cores than it has says so here)
     csd = {key: getattr(cs, key) for key in ("A_p", "b_p", "NA_E", "yp", "z0", "y0")}
     csd.update(P=raw["P"], q=raw["q"], r=raw["r"], M=raw["M"], s=raw["s"], c=raw["c"], d=raw["d"],
                F=raw["F"])
@@ -124,7 +145,7 @@ def cpu_baseline(raw, cs, B, dtype, budget_s, rng=1.0):
         rates = {}
         # (LMI sets: batched eigvalsh of 20 x 20 matrices does not scale past a few threads and collapses beyond)
         candidates = (1, 4, 8, 16) if len(raw["F"]) else (1, 4, 8, 16, 32, 64, cores)
-        for threads in sorted({t for t in candidates if t <= cores}):
+        for threads in sorted({t for t in candidates if t <= min(cores, allowed)}):
             torch.set_num_threads(threads)
             _note(f"cpu baseline probe, {threads} threads")
             first = timed(probe)
@@ -172,9 +193,11 @@ def _sync(on_gpu):
         torch.cuda.synchronize()
 
 
-def timed_loop(step, x, steps, warmup, use_dist, graph=False, on_gpu=True):
+def timed_loop(step, x, steps, warmup, use_dist, graph=False, on_gpu=True, last=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; returns (wall seconds,
-    device ms per step from HIP events recorded on the launch stream; on the CPU dry run: the wall time)."""
+    device ms per step from HIP events recorded on the launch stream; on the CPU dry run: the wall time).
+    ``last``: a dict that receives, under "y", what the final timed step returned."""
+    y = None
     with torch.no_grad():
         replay, per = step, 1
         if graph:
@@ -190,8 +213,8 @@ def timed_loop(step, x, steps, warmup, use_dist, graph=False, on_gpu=True):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 for _ in range(per):
-                    step(x)
-            replay = lambda _x: g.replay()          # noqa: E731
+                    y_graph = step(x)
+            replay = lambda _x: (g.replay(), y_graph)[1]          # noqa: E731  (the graph's last step writes y_graph)
         for _ in range(-(-warmup // per)):
             replay(x)
         _sync(on_gpu)
@@ -204,7 +227,7 @@ def timed_loop(step, x, steps, warmup, use_dist, graph=False, on_gpu=True):
         if on_gpu:
             ev0.record()
         for _ in range(steps // per):
-            replay(x)
+            y = replay(x)
         if on_gpu:
             ev1.record()
         _sync(on_gpu)
@@ -212,6 +235,8 @@ def timed_loop(step, x, steps, warmup, use_dist, graph=False, on_gpu=True):
             dist.barrier()
         _sync(on_gpu)
         elapsed = time.perf_counter() - t0
+    if last is not None:
+        last["y"] = y
     return elapsed, (ev0.elapsed_time(ev1) if on_gpu else elapsed * 1e3) / steps
 
 
@@ -220,6 +245,7 @@ def settle(step, x, steps, warmup, graph, on_gpu):
     returns {"first_window_ms", "settled_ms", "windows", "seconds", "converged"} -- per-step device times."""
     t_start = time.perf_counter()
     history = []
+    steps, warmup = min(steps, SETTLE_WINDOW_MAX_STEPS), min(warmup, SETTLE_WINDOW_MAX_STEPS)
     while True:
         _, ms = timed_loop(step, x, steps, warmup, False, graph=graph, on_gpu=on_gpu)
         history.append(ms)
@@ -229,7 +255,8 @@ def settle(step, x, steps, warmup, graph, on_gpu):
             return {"first_window_ms": history[0], "settled_ms": history[-1], "windows": len(history),
                     "seconds": spent, "converged": bool(agree),
                     "what": f"untimed windows of W+K steps until two in a row agree within {SETTLE_TOL:.0%} "
-                            f"(at least {SETTLE_MIN_S:g} s, at most {SETTLE_MAX_S:g} s); the W+K measurement follows"}
+                            f"(at least {SETTLE_MIN_S:g} s, at most {SETTLE_MAX_S:g} s; W and K capped at "
+                            f"{SETTLE_WINDOW_MAX_STEPS} each); the W+K measurement follows"}
 
 
 L3_BYTES = 256 << 20       # MI355X Infinity Cache (MI355X_MICROARCH.md): FETCH_SIZE / WRITE_SIZE count its hits as traffic
@@ -296,6 +323,23 @@ def profiled_traffic(config, dtype_tag, batch, kernel_tag):
         if traffic is not None:
             best = (traffic, os.path.relpath(path, REPO))
     return best
+
+
+def dump_outputs(out_dir, y, k):
+    """``--dump-outputs``: ``y`` (what the last timed step returned) as ``out_dir/y.npy``, rows x k in its own dtype;
+    above DUMP_MAX_BYTES a fixed sample of its rows (``torch.randperm`` seeded with 0, ascending) -- the same rows for
+    the same arguments, whatever build computed them."""
+    import numpy as np
+    y = y.detach().reshape(-1, k)
+    rows = y.shape[0]
+    keep = max(1, DUMP_MAX_BYTES // (k * y.element_size()))
+    if rows > keep:
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        y = y[idx.to(y.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "y.npy")
+    np.save(path, y.cpu().numpy())
+    _note(f"wrote {path}: {y.shape[0]} of {rows} rows x {k}, {str(y.dtype).split('.')[-1]}")
 
 
 def main(argv=None):
@@ -397,29 +441,37 @@ def main(argv=None):
           f"(first {settled['first_window_ms']:.4f} ms, last {settled['settled_ms']:.4f} ms); timing the projection")
     # ---- rank 0 alone (the others wait at the barrier behind it): what one GPU does with nobody else on the node busy
     solo_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             _, solo_ms = timed_loop(module_step, x, args.steps, args.warmup, False, graph=graph, on_gpu=on_gpu)
         dist.barrier()
     # ---- the projection alone (the whole step at N = 1)
-    elapsed_p, dev_ms = timed_loop(module_step, x, args.steps, args.warmup, use_dist, graph=graph, on_gpu=on_gpu)
+    if pairs > 1:
+        module_step.i = 0                        # (the rotation starts at x itself: the last step's batch follows from W and K)
+    timed_out = {}
+    elapsed_p, dev_ms = timed_loop(module_step, x, args.steps, args.warmup, use_dist, graph=graph, on_gpu=on_gpu,
+                                   last=timed_out)
     if on_gpu:
         from rayen_amd import _lib as _klib
         timed_kernel = _klib.load().rayen_last_forward_kernel()      # which instruction stream served the TIMED launches
-    # ---- the same launches on ONE (x, y) pair (128 MiB at config 3: resident in the Infinity Cache) -- reported beside
-    l3_ms = None
     if pairs > 1:
         module_step.ring = [None] * pairs
+    # ---- the same launches on ONE (x, y) pair (128 MiB at config 3: resident in the Infinity Cache) -- reported beside
+    l3_ms = None
+    if pairs > 1 and args.full:
         _, l3_ms = timed_loop(single_step, x, args.steps, args.warmup, False, graph=graph, on_gpu=on_gpu)
     with torch.no_grad():
         y = single_step(x)
     # ---- projection + all-gather of y (the north_star's multi-GPU step)
     elapsed_g = None
     if gather:
-        elapsed_g, dev_ms_g = timed_loop(sharded, x, args.steps, args.warmup, use_dist, on_gpu=on_gpu)
+        elapsed_g, dev_ms_g = timed_loop(sharded, x, args.steps, args.warmup, use_dist, on_gpu=on_gpu, last=timed_out)
+        last["dev_ms_gather"] = dev_ms_g
+        if args.dump_outputs and rank == 0:
+            timed_out["y"] = sharded.gathered()                    # (the buffer in global row order, before any later step)
+    if gather and args.full:
         got = sharded.rows_of(rank).reshape(-1, cs.k)[:B]
         assert torch.equal(got, y[:, :, 0]), "gathered rows differ from the local projection"
-        last["dev_ms_gather"] = dev_ms_g
         sharded(x, trace=True)                                     # one more step, time-stamped per chunk (untimed)
         last["gather_trace"] = sharded.last_trace
         # the collective alone, same buffers and chunks, nothing projected: what the links do with the CUs idle
@@ -444,12 +496,15 @@ def main(argv=None):
     sl = y[: min(B, 65536), :, 0].double().cpu().numpy()
     row_violation = cs.getViolationRows(sl) if B else sl[:, 0]
     max_violation = float(row_violation.max()) if B else 0.0
-    violation_detail = workloads.violation_report(cs, sl[:8192]) if B else None
+    violation_detail = workloads.violation_report(cs, sl[:8192]) if (B and args.full) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_out["y"], cs.k)
 
     # the same rows with the inward bias on (RAYEN_PREPARE_INWARD_BIAS, include/rayen_hip.h: the fp32 images evaluate
     # (1 + eps) kappa, clipped samples stop eps short of the boundary) -- feasibility before / after and what it costs in parity
     bias_report = None
-    if on_gpu and world == 1 and rank == 0 and not args.mapper and dtype == torch.float32 and B and not args.no_families:
+    if on_gpu and world == 1 and rank == 0 and not args.mapper and dtype == torch.float32 and B and not args.no_families \
+            and args.full:
         bias_report = {"what": "fp64 residuals of the fp32 outputs on the same rows, pack built with RAYEN_INWARD_BIAS=eps (0 = the "
                                "reference's step; the module's default is 2^-20); shift = per-row inf-norm distance from the eps = 0 "
                                "outputs, relative to the row",
@@ -596,7 +651,7 @@ def main(argv=None):
                                                                      "step) / (N x rank 0's rate with the other ranks idle)"})
                 out["scaling_efficiency"] = out["no_gather"]["scaling_efficiency"]
                 out["scaling_efficiency_of"] = "value_no_gather (the projection alone; `value` includes the all-gather of y)"
-            if gather:
+            if gather and args.full:
                 recv = (total_rows - B) * cs.k * (4 if dtype == torch.float32 else 8)
                 peers = max(world - 1, 1)
                 link_peak = peers * XGMI_GBPS_PER_LINK_PER_DIRECTION
@@ -616,7 +671,7 @@ def main(argv=None):
                                  "per_chunk_rank0": last.get("gather_trace"),
                                  "how_to_read": "overlap happened if chunk c's gather_end_ms is not behind chunk c+1's "
                                                 "projection_end_ms by the gather's own duration"}
-        if on_gpu and world == 1 and not args.mapper and not args.no_families and B:
+        if on_gpu and world == 1 and not args.mapper and not args.no_families and B and args.full:
             # the training step of the same workload: forward with the arg-max record, then the backward (the two launches
             # `loss.backward()` through the layer costs, examples/main.py:166-171), timed the same way, outside `value`
             g_in = torch.empty(B, cs.k, device=device, dtype=dtype).uniform_(-1, 1)
@@ -637,7 +692,7 @@ def main(argv=None):
                 "backward_kernel": bwd_names.get(int(info.bwd_f32), str(info.bwd_f32)) if dtype == torch.float32 else "fp64 kernels",
                 "backward_check_pair_vs_fp64": info.bwd32_check_pair, "backward_check_exact_vs_fp64": info.bwd32_check_exact,
                 "clipped_fraction": float((k_rec > 1).double().mean())}
-        if on_gpu and world == 1 and not args.mapper and not args.no_families and B and dtype == torch.float32 \
+        if on_gpu and world == 1 and not args.mapper and not args.no_families and B and dtype == torch.float32 and args.full \
                 and cs.n <= 64 and cs.n % 4 == 0 and dp.mapper_fusable(cs.n):
             # the same workload behind the module's own mapper (create_map=True, the reference's default: rayen/constraint_module.py
             # :259-263, 525): x -> v = Wm x + b -> y in ONE launch, timed the same way, outside `value`
@@ -664,7 +719,7 @@ def main(argv=None):
         if args.mapper:
             fused = on_gpu and (not args.no_fuse) and dtype == torch.float32 and dp.mapper_fusable(args.mapper)
             out["config"]["mapper"] = f"nn.Linear({args.mapper}, {cs.n}) " + ("fused into the projection kernel" if fused else "as its own GEMM")
-        if split and world == 1 and not args.mapper and not args.no_families:
+        if split and world == 1 and not args.mapper and not args.no_families and args.full:
             # the same workload on the other fp32 families (RayenPackDesc.fp32_mode / RAYEN_FP32_MODE at pack
             # creation), timed the same way, so that one line carries all of them
             if served_by == getattr(_lib, "KERNEL_PAIR_WL", -1):
@@ -723,7 +778,7 @@ def main(argv=None):
             out["fp32_family_check"] = {"pair_vs_fp64": info.fp32_check_pair, "triple_vs_fp64": info.fp32_check_split,
                                         "exact_vs_fp64": info.fp32_check_exact,
                                         "what": "worst row error on the pack-creation probe directions (-1: not measured)"}
-        if on_gpu and world == 1 and not args.no_cpu_baseline and not args.mapper:
+        if on_gpu and world == 1 and not args.no_cpu_baseline and not args.mapper and args.full:
             out["cpu_baseline"] = cpu_baseline(raw, cs, B, dtype, args.cpu_seconds, rng)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         line = json.dumps(out)

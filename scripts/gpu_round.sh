@@ -14,12 +14,12 @@ tests)
   tail -5 $out/pytest.log ;;
 bench)
   for cfg in c3 c1 c2 c4 c5 c5r; do
-    timeout 600 python bench.py --config $cfg > $out/bench_${cfg}_fp32.json 2> $out/bench_${cfg}_fp32.err
+    timeout 600 python bench.py --full --config $cfg > $out/bench_${cfg}_fp32.json 2> $out/bench_${cfg}_fp32.err
   done
-  timeout 600 python bench.py --config c3 --dtype fp64 > $out/bench_c3_fp64.json 2> $out/bench_c3_fp64.err
-  timeout 600 python bench.py --config c4 --dtype fp64 > $out/bench_c4_fp64.json 2> $out/bench_c4_fp64.err
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_c3_driver_like.json 2>&1
-  timeout 600 python bench.py --force-dist --no-cpu-baseline > $out/bench_c3_forcedist.json 2>&1
+  timeout 600 python bench.py --full --config c3 --dtype fp64 > $out/bench_c3_fp64.json 2> $out/bench_c3_fp64.err
+  timeout 600 python bench.py --full --config c4 --dtype fp64 > $out/bench_c4_fp64.json 2> $out/bench_c4_fp64.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_c3_driver_like.json 2>&1
+  timeout 600 python bench.py --full --force-dist --no-cpu-baseline > $out/bench_c3_forcedist.json 2>&1
   head -c 600 $out/bench_c3_fp32.json; echo ;;
 prof)
   for cfg in ${PROF_CONFIGS:-c3 c4 c2 c5 c1}; do
@@ -36,10 +36,10 @@ bwd)
   timeout 2000 python scripts/ubench/lmi_sweep.py --oracle 2>&1 | grep "^{" > $out/lmi_sweep.txt
   cat $out/bwd_c5.txt ;;
 mapper)
-  timeout 600 python bench.py --mapper 64 --no-cpu-baseline > $out/bench_c3_mapper64_fused.json 2> $out/bench_c3_mapper64_fused.err
-  timeout 600 python bench.py --mapper 64 --no-fuse --no-cpu-baseline > $out/bench_c3_mapper64_twoop.json 2> $out/bench_c3_mapper64_twoop.err
-  timeout 600 python bench.py --config c5 --mapper 32 --no-cpu-baseline > $out/bench_c5_mapper32_fused.json 2>&1
-  timeout 600 python bench.py --config c5 --mapper 32 --no-fuse --no-cpu-baseline > $out/bench_c5_mapper32_twoop.json 2>&1
+  timeout 600 python bench.py --full --mapper 64 --no-cpu-baseline > $out/bench_c3_mapper64_fused.json 2> $out/bench_c3_mapper64_fused.err
+  timeout 600 python bench.py --full --mapper 64 --no-fuse --no-cpu-baseline > $out/bench_c3_mapper64_twoop.json 2> $out/bench_c3_mapper64_twoop.err
+  timeout 600 python bench.py --full --config c5 --mapper 32 --no-cpu-baseline > $out/bench_c5_mapper32_fused.json 2>&1
+  timeout 600 python bench.py --full --config c5 --mapper 32 --no-fuse --no-cpu-baseline > $out/bench_c5_mapper32_twoop.json 2>&1
   cat $out/bench_c3_mapper64_fused.json | head -c 400; echo ;;
 esac
 done

@@ -292,7 +292,8 @@ def test_bench_entry_self_launches_for_gpus_2():
     """``python bench.py --gpus 2`` WITHOUT torchrun (WORLD_SIZE unset) must produce the line: it re-runs itself under
     torch.distributed.run.  Host dry run (gloo, the product's packed torch evaluator as the projection): what is under
     test is the launcher, the rank plumbing, the step and every field the first hardware run will be read by."""
-    line = _bench_line(["--gpus", "2", "--config", "c2", "--batch", "200", "--steps", "3", "--warmup", "1", "--chunks", "2"])
+    line = _bench_line(["--gpus", "2", "--config", "c2", "--batch", "200", "--steps", "3", "--warmup", "1", "--chunks", "2",
+                        "--full"])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["backend"]["name"] == "gloo"
     assert line["config"]["global_batch"] == 400 and line["scaling"] == "weak"
     assert line["value"] > 0 and line["steps"] == 3 and line["warmup"] == 1
@@ -321,3 +322,35 @@ def test_bench_entry_strong_scaling_shards_the_config_batch():
     line = _bench_line(["--gpus", "2", "--config", "c1", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--no-gather"])
     assert line["config"]["global_batch"] == 500 and line["config"]["batch_per_gpu"] == 250
     assert "gather" not in line and line["no_gather"]["value"] > 0
+
+
+def _host_projection(config, rows, rank):
+    """What ``bench.py`` projects on rank ``rank`` of the host dry run: the module of ``config`` (seed 0) on the rank's
+    seeded inputs."""
+    sys.path.insert(0, REPO)
+    from rayen_amd import workloads
+    from rayen_amd.constraint_module import ConstraintModule
+    cs = workloads.build_constraints(workloads.make_raw(config, seed=0))
+    layer = ConstraintModule(cs, method="RAYEN", create_map=False)
+    layer.check_nan = False
+    rng = workloads.CONFIGS[config][3]
+    x = torch.empty(rows, cs.n, 1).uniform_(-rng, rng, generator=torch.Generator().manual_seed(1000 + rank))
+    with torch.no_grad():
+        return layer(x)[:, :, 0].numpy()
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """A run without ``--full`` measures the headline alone; ``--dump-outputs`` writes what the last timed step returned
+    (here the all-gather of two ranks: every rank's rows in global order), the same for the same arguments."""
+    args = ["--gpus", "2", "--config", "c2", "--batch", "64", "--steps", "3", "--warmup", "1"]
+    line = _bench_line(args + ["--dump-outputs", str(tmp_path / "a")])
+    _bench_line(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["violations_checked_rows"] == 64 and line["violations_gt_1e-6"] == 0
+    assert "gather" not in line and "solo_rank0_ms_per_step" not in line["no_gather"]
+    assert line["violation_detail"] is None and "l3_resident" not in line["roofline"]
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert a.dtype == np.float32 and a.shape == (128, 16)
+    assert np.array_equal(a, b)
+    want = np.concatenate([_host_projection("c2", 64, rank) for rank in range(2)])
+    np.testing.assert_allclose(a, want, rtol=1e-5, atol=1e-6)
