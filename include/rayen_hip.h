@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 8
+#define RAYEN_ABI_VERSION 9
 
 enum {
   RAYEN_OK = 0,
@@ -330,6 +330,32 @@ int rayen_ray_project_mapped_image_f32(const RayenPack* pack, const float* x, in
                                        int32_t in_dim, const void* image, float* v_out, int64_t ldvo,
                                        float* y, int64_t ldy, float* kappa, int32_t* active,
                                        int32_t* nan_flag, void* stream);
+
+/* ---- method='Bar' (ABI v9): the reference's barycentric layer (rayen/constraint_module.py:479-486)
+ *
+ *     lambda = softmax(q[:, :nv]),  mu = |q[:, nv:nv+nr]|,  y = G [lambda; mu] + yp,   G = NA_E [V R]  (k x (nv+nr))
+ *
+ * A RayenBarPack holds fp32 and fp64 device images of G (fp64, k x (nv+nr), row-major) and yp [k], uploaded once on
+ * the current device; it is immutable afterwards.  1 <= k <= 64 (else RAYEN_E_UNSUPPORTED at creation); a call whose
+ * image of G does not fit the kernels' LDS ((round_up(nv+nr, 4) + 1) * K * sizeof(T) bytes, K = k rounded up to 4, 8, 16, 32 or 64,
+ * at most 160 KiB) returns RAYEN_E_UNSUPPORTED.
+ *
+ * forward: q [B, ldq] (first nv+nr columns read), y [B, ldy] (first k columns written); rowstat [B] or NULL receives the
+ *   per-row log-sum-exp of q[:, :nv] (what the backward needs; 0 when nv = 0); *nan_flag |= 1 where a y is NaN.
+ * backward: grad_y [B, k] contiguous; grad_q [B, ldq] receives its first nv+nr columns:
+ *   lambda (g_v - <lambda, g_v>) on the vertex columns, sign(q) g_r on the ray columns, g = G' grad_y per row.
+ * Any B >= 0; asynchronous on the stream, no allocation, graph-capturable. */
+typedef struct RayenBarPack RayenBarPack;
+int rayen_bar_pack_create(const double* G, const double* yp, int32_t k, int32_t nv, int32_t nr, RayenBarPack** out);
+void rayen_bar_pack_destroy(RayenBarPack* pack);
+int rayen_bar_forward_f32(const RayenBarPack* pack, const float* q, int64_t B, int64_t ldq, float* y, int64_t ldy,
+                          float* rowstat, int32_t* nan_flag, void* stream);
+int rayen_bar_forward_f64(const RayenBarPack* pack, const double* q, int64_t B, int64_t ldq, double* y, int64_t ldy,
+                          double* rowstat, int32_t* nan_flag, void* stream);
+int rayen_bar_backward_f32(const RayenBarPack* pack, const float* q, int64_t ldq, const float* rowstat,
+                           const float* grad_y, int64_t B, float* grad_q, void* stream);
+int rayen_bar_backward_f64(const RayenBarPack* pack, const double* q, int64_t ldq, const double* rowstat,
+                           const double* grad_y, int64_t B, double* grad_q, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import os
 
 from ._build import LIBRARY
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 SEG_LIN, SEG_QUAD_SYM, SEG_QUAD_FAC, SEG_SOC, SEG_LMI = range(5)
 E_UNSUPPORTED = -6      # RAYEN_E_UNSUPPORTED (include/rayen_hip.h)
@@ -30,6 +30,8 @@ EXPORTS = (
     "rayen_pair_schedule", "rayen_reserve_cus",
     "rayen_products_rows", "rayen_products_served", "rayen_ray_project_from_products_f32", "rayen_ray_project_from_products_f64",
     "rayen_ray_project_bwd_coefficients_f32", "rayen_ray_project_bwd_coefficients_f64",
+    "rayen_bar_pack_create", "rayen_bar_pack_destroy", "rayen_bar_forward_f32", "rayen_bar_forward_f64",
+    "rayen_bar_backward_f32", "rayen_bar_backward_f64",
 )
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
@@ -141,6 +143,17 @@ def load():
     lib.rayen_ray_project_mapped_image_f32.restype = ctypes.c_int
     lib.rayen_ray_project_mapped_image_f32.argtypes = [p, p, i64, i64, ctypes.c_int32, p, p, i64, p, i64,
                                                        p, i32p, i32p, p]
+    lib.rayen_bar_pack_create.restype = ctypes.c_int
+    lib.rayen_bar_pack_create.argtypes = [p, p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_void_p)]
+    lib.rayen_bar_pack_destroy.restype = None
+    lib.rayen_bar_pack_destroy.argtypes = [p]
+    for name in ("rayen_bar_forward_f32", "rayen_bar_forward_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [p, p, i64, i64, p, i64, p, i32p, p]
+    for name in ("rayen_bar_backward_f32", "rayen_bar_backward_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [p, p, i64, p, p, i64, p, p]
     if lib.rayen_abi_version() != ABI_VERSION:
         raise RuntimeError(f"librayen_hip.so ABI {lib.rayen_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -16,8 +16,10 @@ constants with plain torch ops on the caller's device (``rayen_amd/eager.py``; t
 
 ``method='RAYEN'`` (the default) is the hot path this package accelerates; its older step rule
 ``'RAYEN_old'`` (:460-466) runs on the same kernels; ``'UU'`` is the identity and kept because it
-is free; the paper baselines (``UP, PP, DC3, Bar``) are out of scope and raise
-``NotImplementedError``.
+is free; ``'Bar'`` (the barycentric baseline, :124-132 and :479-486) converts the linear part of the set to
+vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kernel per direction
+(``rayen_amd/csrc/rayen_bar.hip``).  The other paper baselines (``UP, PP, DC3``) need solvers this package
+does not carry and raise ``NotImplementedError``.
 
 Documented deviation: for an SOC whose ray never meets the cone (negative
 discriminant with ``c' < 0``) the reference's assert at :342 fires (or NaN under
@@ -66,8 +68,10 @@ class ConstraintModule(torch.nn.Module):
         super().__init__()
 
         self.method = method
-        if method not in ('RAYEN', 'RAYEN_old', 'UU'):
-            if method in ('UP', 'PP', 'DC3', 'Bar'):
+        if method == 'Bar' and cs.has_quadratic_constraints:
+            raise Exception(f"Method {method} cannot be used with quadratic constraints")     # (:24-25)
+        if method not in ('RAYEN', 'RAYEN_old', 'UU', 'Bar'):
+            if method in ('UP', 'PP', 'DC3'):
                 raise NotImplementedError(
                     f"method '{method}' is one of the reference's comparison baselines; rayen_amd "
                     "implements the RAYEN projection only")
@@ -129,12 +133,29 @@ class ConstraintModule(torch.nn.Module):
             self.register_buffer("all_delta", torch.stack(all_delta))
             self.register_buffer("all_phi", torch.stack(all_phi))
 
+        if self.method == 'Bar':
+            # vertices and rays of the linear part {z : A_p z <= b_p} (:124-132); cones and LMIs are not imposed
+            if cs.has_soc_constraints or cs.has_lmi_constraints:
+                warnings.warn("method 'Bar' imposes the linear constraints only: the second-order-cone and LMI "
+                              "constraints of this set are not imposed", UserWarning, stacklevel=2)
+            from .vrep import H_to_V
+            V, R = H_to_V(cs.A_p, cs.b_p)
+            self.register_buffer("V", torch.Tensor(V))
+            self.register_buffer("R", torch.Tensor(R))
+            self.num_vertices = self.V.shape[1]
+            self.num_rays = self.R.shape[1]
+            assert (self.num_vertices + self.num_rays) > 0
+            self._bar_packs = {}
+
         if self.method == 'RAYEN':
             self.forwardForMethod = self.forwardForRAYEN
             self.dim_after_map = self.n
         elif self.method == 'RAYEN_old':
             self.forwardForMethod = self.forwardForRAYENOld
             self.dim_after_map = self.n + 1
+        elif self.method == 'Bar':
+            self.forwardForMethod = self.forwardForBar
+            self.dim_after_map = self.num_vertices + self.num_rays
         else:  # 'UU'
             self.forwardForMethod = self.forwardForUU
             self.dim_after_map = self.k
@@ -169,6 +190,7 @@ class ConstraintModule(torch.nn.Module):
         self._fast = {}
         self.__dict__["_unsupported"] = set()
         self.__dict__.pop("_eager", None)
+        self.__dict__["_bar_packs"] = {}
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -209,6 +231,7 @@ class ConstraintModule(torch.nn.Module):
         state["_fast"] = {}
         state["_unsupported"] = set()
         state.pop("_eager", None)
+        state["_bar_packs"] = {}
         state.pop("forwardForMethod", None)
         return state
 
@@ -216,7 +239,7 @@ class ConstraintModule(torch.nn.Module):
         super().__setstate__(state)
         self._fast = {}
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
-                                 'UU': self.forwardForUU}[self.method]
+                                 'UU': self.forwardForUU, 'Bar': self.forwardForBar}[self.method]
 
     # ------------------------------------------------------------------ the projection
     def _project(self, q, old_head=False):
@@ -284,6 +307,54 @@ class ConstraintModule(torch.nn.Module):
 
     def forwardForUU(self, q):
         return q
+
+    # ------------------------------------------------------------------ method='Bar'
+    def bar_pack(self, device):
+        """(pack, pack_id): ``G = NA_E [V R]`` and ``yp`` of the CURRENT buffers resident on ``device`` (built on first
+        use; forgotten by ``.to()`` and ``load_state_dict``, so a loaded ``V`` / ``R`` is what the kernels read)."""
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        packs = self.__dict__.setdefault("_bar_packs", {})
+        entry = packs.get(index)
+        if entry is None:
+            NA_E = self.NA_E.detach().double().cpu()
+            G = torch.cat([NA_E @ self._bar_generators(self.V), NA_E @ self._bar_generators(self.R)], dim=1)
+            bp = ops.BarPack(G.numpy(), self.yp.detach().double().cpu().numpy(), self.num_vertices, self.num_rays, index)
+            entry = packs[index] = (bp, ops.register_pack(bp))
+        return entry
+
+    def _bar_generators(self, X):
+        return X.detach().double().cpu().reshape(self.n, -1) if X.numel() else torch.zeros((self.n, 0), dtype=torch.float64)
+
+    def _bar_reference(self, q):
+        """The reference formula (:479-486) in plain torch ops on ``q``'s device and dtype."""
+        nv, nr = self.num_vertices, self.num_rays
+        lambdas = nn.functional.softmax(q[:, 0:nv, 0:1], dim=1)
+        mus = torch.abs(q[:, nv:nv + nr, 0:1])
+        z = (self.V.to(q.dtype) @ lambdas if nv else 0) + (self.R.to(q.dtype) @ mus if nr else 0)
+        return self.NA_E.to(q.dtype) @ z + self.yp.to(q.dtype)
+
+    def forwardForBar(self, q):
+        if not q.is_cuda:
+            return self._bar_reference(q)        # host tensors: the reference's formula, differentiable by autograd
+        q2 = torch.flatten(q, 1)
+        if q2.dtype not in (torch.float32, torch.float64):
+            return self.forwardForBar(q2.float().unsqueeze(2)).to(q2.dtype)     # 16-bit activations: computed in fp32
+        if self._refused(q2):
+            return self._bar_reference(q2.unsqueeze(2))
+        try:
+            bp, pack_id = self.bar_pack(q2.device)
+            if not (torch.is_grad_enabled() and q2.requires_grad) and not torch.compiler.is_compiling():
+                y, _ = ops.bar_forward_raw(q2, bp, want_rowstat=False)      # plain inference: straight to the C ABI
+            else:
+                y, _ = torch.ops.rayen_amd.bar_project(q2, pack_id)
+        except _lib.RayenError as err:
+            if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
+                raise
+            warnings.warn(f"rayen_amd: no HIP kernel serves this Bar layer ({err}); this module now runs the reference "
+                          "formula with torch ops on " + str(q2.device), RuntimeWarning, stacklevel=3)
+            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, False))
+            return self._bar_reference(q2.unsqueeze(2))
+        return y.unsqueeze(2)
 
     # ------------------------------------------------------------------ reference helper surface
     def getDimAfterMap(self):
@@ -372,11 +443,11 @@ class ConstraintModule(torch.nn.Module):
             q = torch.unsqueeze(self.mapper(x2), dim=2)
             y = self.forwardForMethod(q)
 
-        if __debug__ and self.check_nan and self.method in ('RAYEN', 'RAYEN_old'):
+        if __debug__ and self.check_nan and self.method in ('RAYEN', 'RAYEN_old', 'Bar'):
             if not y.is_cuda or self._refused(y, self.method == 'RAYEN_old'):
                 assert not torch.isnan(y).any(), "the projection produced NaN (NaN in the input?)"     # CM:531
             elif not torch.cuda.is_current_stream_capturing():  # the flag read is a host sync
-                dp, _ = self.device_pack(y.device)
+                dp, _ = self.bar_pack(y.device) if self.method == 'Bar' else self.device_pack(y.device)
                 if int(dp.nan_flag.item()) != 0:
                     dp.nan_flag.zero_()
                     raise AssertionError("the projection produced NaN (NaN in the input?)")

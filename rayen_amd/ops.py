@@ -408,3 +408,122 @@ def _mapped_backward(ctx, grad_y, grad_kappa, grad_active, grad_v_out):
 
 
 ray_project_mapped.register_autograd(_mapped_backward, setup_context=_mapped_setup_context)
+
+
+# ------------------------------------------------------------------------------------------------
+# method='Bar' (rayen/constraint_module.py:479-486): y = G [softmax(q_v); |q_r|] + yp on rayen_bar.hip
+# ------------------------------------------------------------------------------------------------
+
+class BarPack:
+    """Owner of one ``RayenBarPack*``: fp32 and fp64 images of ``G = NA_E [V R]`` (k x (nv + nr)) and ``yp`` on one
+    device, plus the NaN flag its forward raises.  Immutable, so a captured graph may keep using it."""
+
+    def __init__(self, G, yp, nv, nr, device_index):
+        import numpy as np
+        self.k, self.nv, self.nr = int(G.shape[0]), int(nv), int(nr)
+        self.device_index = int(device_index)
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        yp = np.ascontiguousarray(np.reshape(yp, -1), dtype=np.float64)
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device_index):
+            _lib.check(_lib.load().rayen_bar_pack_create(G.ctypes.data, yp.ctypes.data, self.k, self.nv, self.nr,
+                                                         ctypes.byref(handle)), "rayen_bar_pack_create")
+            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+        self.handle = handle
+
+    @property
+    def width(self):
+        return self.nv + self.nr
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.load().rayen_bar_pack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bar_check(q, pack):
+    if not q.is_cuda:
+        raise RuntimeError("rayen_amd: the Bar layer's HIP op runs on an MI355X (HIP) device only; got a "
+                           f"{q.device} tensor")
+    if q.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
+    if q.dim() != 2 or q.shape[1] < pack.width:
+        raise RuntimeError(f"rayen_amd: expected q of shape [B, >= {pack.width}], got {tuple(q.shape)}")
+    if q.device.index != pack.device_index:
+        raise RuntimeError("rayen_amd: input and Bar pack live on different devices")
+
+
+def bar_forward_raw(q, pack, want_rowstat=True):
+    """``(y [B, k], rowstat [B] | None)`` through ``rayen_bar_forward_*``; ``rowstat`` is the per-row log-sum-exp of
+    the vertex logits (the backward's input)."""
+    _bar_check(q, pack)
+    if q.stride(1) != 1:
+        q = q.contiguous()
+    B = q.shape[0]
+    y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
+    rowstat = torch.empty((B,), dtype=q.dtype, device=q.device) if want_rowstat else None
+    with _on_device(q.device):
+        code = _entry("rayen_bar_forward_f32" if q.dtype == torch.float32 else "rayen_bar_forward_f64")(
+            pack.handle, _ptr(q), B, q.stride(0) if B else pack.width, _ptr(y), pack.k, _ptr(rowstat),
+            _ptr(pack.nan_flag), _stream(q.device.index))
+    _lib.check(code, "rayen_bar_forward")
+    return y, rowstat
+
+
+def bar_backward_raw(q, rowstat, grad_y, pack):
+    """``grad_q`` (same shape as ``q``; columns beyond ``nv + nr`` are zero) through ``rayen_bar_backward_*``."""
+    _bar_check(q, pack)
+    q = q.contiguous()
+    grad_y = grad_y.to(q.dtype).contiguous()
+    rowstat = rowstat.contiguous()
+    B = q.shape[0]
+    grad_q = torch.empty_like(q) if q.shape[1] == pack.width else torch.zeros_like(q)
+    with _on_device(q.device):
+        code = _entry("rayen_bar_backward_f32" if q.dtype == torch.float32 else "rayen_bar_backward_f64")(
+            pack.handle, _ptr(q), q.shape[1], _ptr(rowstat), _ptr(grad_y), B, _ptr(grad_q), _stream(q.device.index))
+    _lib.check(code, "rayen_bar_backward")
+    return grad_q
+
+
+@torch.library.custom_op("rayen_amd::bar_project", mutates_args=())
+def bar_project(q: torch.Tensor, pack_id: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(y [B, k], rowstat [B])``: the Bar layer's forward on torch's current stream."""
+    return bar_forward_raw(q, _pack(pack_id))
+
+
+@bar_project.register_fake
+def _(q, pack_id):
+    pack = _pack(pack_id)
+    return q.new_empty((q.shape[0], pack.k)), q.new_empty((q.shape[0],))
+
+
+@torch.library.custom_op("rayen_amd::bar_project_bwd", mutates_args=())
+def bar_project_bwd(q: torch.Tensor, rowstat: torch.Tensor, grad_y: torch.Tensor, pack_id: int) -> torch.Tensor:
+    return bar_backward_raw(q, rowstat, grad_y, _pack(pack_id))
+
+
+@bar_project_bwd.register_fake
+def _(q, rowstat, grad_y, pack_id):
+    return torch.empty_like(q)
+
+
+def _bar_setup_context(ctx, inputs, output):
+    q, pack_id = inputs
+    ctx.pack_id = pack_id
+    ctx.save_for_backward(q, output[1])
+
+
+def _bar_backward(ctx, grad_y, grad_rowstat):
+    q, rowstat = ctx.saved_tensors
+    if grad_y is None:
+        return None, None
+    return torch.ops.rayen_amd.bar_project_bwd(q, rowstat, grad_y, ctx.pack_id), None
+
+
+bar_project.register_autograd(_bar_backward, setup_context=_bar_setup_context)
