@@ -1,5 +1,6 @@
 // C-ABI entry points of librayen_hip.so (declared in include/rayen_hip.h).
 #include "rayen_internal.h"
+#include "rayen_pair_image.h"
 
 #include <atomic>
 #include <cmath>
@@ -45,20 +46,6 @@ template <> GenericImage<double>& image_of<double>(const RayenPack* p) { return 
 
 // which kernel family served this thread's most recent forward call (rayen_last_forward_kernel)
 thread_local int g_last_forward = RAYEN_KERNEL_NONE;
-
-// Schedules of the f16-pair forward (same arithmetic): 3 (default, round 6) = the image of W resident in LDS
-// (rayen_mfma_pair_wl.hip) where the pack and the call allow it, else as 1 | 1 (the default of rounds 3-5) = rows of v and y
-// trickled through LDS under the tile walk (rayen_mfma_pair_io.hip) where the call's shape allows it, the W-stationary
-// kernel for mid-size batches | 0 = rayen_mfma_pair.hip always | 2 = W-stationary (rayen_mfma_pair_ws8.hip) where the pack
-// and the call allow it, else as 1.  All bit-identical.  RAYEN_PAIR_IO / rayen_pair_schedule select (A/B runs).
-std::atomic<int>& pair_schedule_cell() {
-  static std::atomic<int> mode([] {
-    const char* e = std::getenv("RAYEN_PAIR_IO");
-    return (e != nullptr && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 3;
-  }());
-  return mode;
-}
-int pair_schedule() { return pair_schedule_cell().load(std::memory_order_relaxed); }
 
 // compute units left free by the persistent grids (rayen_reserve_cus; RAYEN_RESERVE_CUS sets the initial value)
 std::atomic<int>& reserved_cus_cell() {
@@ -880,28 +867,7 @@ static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ld
   const int rc = check_ready<float>(p, false);
   if (rc) return rc;
   if (p->pr32 != nullptr && p->pr32_state == 1 && y != nullptr && !old_mode) {
-    if (pair_schedule() == 3 && mfma_pair_wl_serves(p, p->pr32, v, B, ldv, y, ldy)) {
-      g_last_forward = RAYEN_KERNEL_PAIR_WL;
-      return mfma_pair_wl_forward(p, p->pr32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    }
-    if (pair_schedule() == 2 && mfma_pair_ws8_serves(p, p->pr32, p->ws8_32, v, B, ldv, y, ldy)) {
-      g_last_forward = RAYEN_KERNEL_PAIR_WS;
-      return mfma_pair_ws8_forward(p, p->pr32, p->ws8_32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    }
-    if (pair_schedule() >= 1 && mfma_pair_io_serves(p, p->pr32, v, B, ldv, y, ldy)) {
-      g_last_forward = RAYEN_KERNEL_PAIR_IO;
-      return mfma_pair_io_forward(p, p->pr32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    }
-    // Batches between two groups per CU and one group per resident wave (32 768 <= B < 131 072 on this chip): too small
-    // for the trickled rows to have interior rounds, and the plain kernel leaves SIMDs with one wave or none -- there the
-    // W-stationary kernel is the fastest of the three bit-identical schedules (12.7 against 18.2 us at B = 32 768,
-    // 20.5 / 22.6 at 65 536, 27.2 / 28.4 at 98 304: profiles/bench/r04_midbatch_schedules.txt).
-    if (pair_schedule() == 1 && mfma_pair_ws8_serves(p, p->pr32, p->ws8_32, v, B, ldv, y, ldy)) {
-      g_last_forward = RAYEN_KERNEL_PAIR_WS;
-      return mfma_pair_ws8_forward(p, p->pr32, p->ws8_32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    }
-    g_last_forward = RAYEN_KERNEL_PAIR;
-    return mfma_pair_forward(p, p->pr32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
+    return mfma_pair_family_forward(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream), &g_last_forward);
   }
   if (p->sp32 != nullptr && p->sp32_state == 1 && y != nullptr && !old_mode) {
     g_last_forward = RAYEN_KERNEL_TRIPLE;
@@ -983,14 +949,8 @@ int rayen_ray_project_mapped_image_f32(const RayenPack* p, const float* x, int64
   const int rc = check_ready<float>(p, false);
   if (rc) return rc;
   if (p->pr32 != nullptr && p->pr32_state == 1) {
-    // (round 6: the W-in-LDS schedule with the mapper's image next to W's -- on the pack's own image, shared tiles included)
-    if (pair_schedule() == 3 && mfma_pair_wl_serves_mapped(p, p->pr32, x, B, ldx, in_dim, v_out, ldvo, y, ldy)) {
-      g_last_forward = RAYEN_KERNEL_PAIR_WL;
-      return mfma_pair_wl_forward_mapped(p, p->pr32, x, B, ldx, in_dim, image, v_out, ldvo, y, ldy, kappa, active, nan_flag,
-                                         static_cast<hipStream_t>(stream));
-    }
-    return mfma_pair_forward_mapped(p, p->pr32m != nullptr ? p->pr32m : p->pr32, x, B, ldx, in_dim, image, v_out, ldvo, y, ldy,
-                                    kappa, active, nan_flag, static_cast<hipStream_t>(stream));
+    return mfma_pair_family_forward_mapped(p, x, B, ldx, in_dim, image, v_out, ldvo, y, ldy, kappa, active, nan_flag,
+                                           static_cast<hipStream_t>(stream), &g_last_forward);
   }
   if (p->sp32 == nullptr || p->sp32_state != 1) return RAYEN_E_UNSUPPORTED;
   return mfma_split_forward_mapped(p, p->sp32, x, B, ldx, in_dim, image, v_out, ldvo, y, ldy, kappa, active, nan_flag,

@@ -5,9 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "rayen_hip.h"
+#include "rayen_launch_geometry.h"
 
 namespace rayen {
 
@@ -58,7 +60,7 @@ struct Mfma64BwdgImage; // rayen_mfma_bwdg64.hip
 struct LmiQuadImage;    // rayen_lmi_quad.h
 struct LmiWaveImage;    // rayen_lmi_wave.h
 struct SplitImage;      // rayen_mfma_split.hip
-struct PairImage;       // rayen_mfma_pair.hip
+struct PairImage;       // rayen_pair_image.h
 struct Ws8Image;        // rayen_mfma_pair_ws8.hip
 struct WideImage;       // rayen_wide.hip
 
@@ -127,6 +129,37 @@ int wide_bwd_coefficients(const RayenPack* p, const WideImage* img, const T* Tm,
 // runs beside the projection -- RCCL's all-gather kernels in the multi-GPU step -- needs CUs of its own)
 int launch_simds(int n_simd);
 
+// SIMDs of `device` (CUs x 4), which the images keep for launch_simds(); `fallback` where the query fails
+inline int device_simds(const int device, const int fallback) {
+  hipDeviceProp_t prop;
+  const bool ok = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0;
+  return ok ? prop.multiProcessorCount * 4 : fallback;
+}
+
+// launch geometry of the persistent grids (grid_for_groups, persistent_grid, rows_aligned16): rayen_launch_geometry.h
+
+// run-time (TRACK, STAGED) -> the kernel instance: f(std::bool_constant<track>, std::bool_constant<staged>)
+template <typename F>
+inline void dispatch_track_staged(const bool track, const bool staged, F&& f) {
+  if (!staged) {
+    if (track) f(std::true_type(), std::false_type());
+    else f(std::false_type(), std::false_type());
+  } else {
+    if (track) f(std::true_type(), std::true_type());
+    else f(std::false_type(), std::true_type());
+  }
+}
+
+// host vector -> fresh device allocation; adds its size to *bytes.  *dev is set as soon as the allocation exists, so the
+// image's own free function releases it when a later step fails.
+template <typename T>
+inline bool upload_to_device(const std::vector<T>& host, T** dev, int64_t* bytes) {
+  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return false;
+  if (hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
+  *bytes += (int64_t)(host.size() * sizeof(T));
+  return true;
+}
+
 // generic path (rayen_generic.hip)
 template <typename T>
 int generic_build(const RayenPack* p, GenericImage<T>* img);
@@ -163,11 +196,8 @@ int mfma_split_forward(const RayenPack* p, const SplitImage* img, const float* v
                        float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
                        hipStream_t stream);
 
-// fp32 results on pairs of f16 operands (rayen_mfma_pair.hip); eligibility is mfma_split_eligible's
-int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes);
-int mfma_pair_build_dense(const RayenPack* p, PairImage** out, int64_t* bytes);   // without shared tiles (fused mapper)
-bool mfma_pair_has_halves(const PairImage* img);
-void mfma_pair_free(PairImage* img);
+// fp32 results on pairs of f16 operands (rayen_mfma_pair.hip); the image, its build and the choice among the schedules
+// below: rayen_pair_image.h
 int mfma_pair_forward(const RayenPack* p, const PairImage* img, const float* v, int64_t B, int64_t ldv,
                       float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
                       hipStream_t stream);

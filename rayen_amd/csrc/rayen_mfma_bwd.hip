@@ -328,11 +328,7 @@ int mfma_bwd_build(const RayenPack* p, MfmaBwdImage** out, int64_t* bytes) {
   img->n_items = n_real;
   const std::vector<int32_t> seg_bucket = bucket_table(p, bwd_quad_like, &img->n_dense);
   img->n_segs = (int)p->segs.size();
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   const bool ok =
       hipMalloc(&img->S, frag.size() * sizeof(float)) == hipSuccess &&
       hipMemcpy(img->S, frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
@@ -370,7 +366,6 @@ template <int NKK>
 static int launch_bwd(const RayenPack* p, const MfmaBwdImage* img, const float* v, int64_t B, int64_t ldv,
                       const float* kappa, const int32_t* active, const float* gy, int64_t ldg, float* gv,
                       int64_t ldgv, int old_mode, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  auto aligned = [](const void* ptr, int64_t ld) { return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0); };
   const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
   const int64_t need = old_mode ? 0 : mfma_bwd_workspace_bytes(p, img, B);
   if (need > 0 && workspace != nullptr && workspace_bytes >= need) {
@@ -378,21 +373,17 @@ static int launch_bwd(const RayenPack* p, const MfmaBwdImage* img, const float* 
     int32_t* ws = static_cast<int32_t*>(workspace);
     launch_bucket_sort<float>(kappa, active, B, img->seg_bucket, nb, ws, stream);
     const int64_t max_groups = (B + 63) / 64 + nb;   // (the kernel reads the true count from the workspace)
-    const int64_t rounds = (max_groups + slots - 1) / slots;
-    const int64_t waves = (max_groups + rounds - 1) / rounds;
-    const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
+    const int64_t grid = grid_for_groups(max_groups, slots, kMfmaWaves);
     hipLaunchKernelGGL((mfma_bwd_kernel<NKK, true>), dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream, img->S,
-                       img->items, img->n_items, img->Wrow, p->n, v, B, ldv, aligned(v, ldv) ? 1 : 0, kappa, active,
-                       gy, ldg, aligned(gy, ldg) ? 1 : 0, gv, ldgv, aligned(gv, ldgv) ? 1 : 0, 0, ws, nb);
+                       img->items, img->n_items, img->Wrow, p->n, v, B, ldv, rows_aligned16(v, ldv) ? 1 : 0, kappa, active,
+                       gy, ldg, rows_aligned16(gy, ldg) ? 1 : 0, gv, ldgv, rows_aligned16(gv, ldgv) ? 1 : 0, 0, ws, nb);
     return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
   }
   const int64_t n_groups = (B + RAYEN_BWD_NT * 32 - 1) / (RAYEN_BWD_NT * 32);
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
+  const int64_t grid = grid_for_groups(n_groups, slots, kMfmaWaves);
   hipLaunchKernelGGL((mfma_bwd_kernel<NKK, false>), dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream, img->S,
-                     img->items, img->n_items, img->Wrow, p->n, v, B, ldv, aligned(v, ldv) ? 1 : 0, kappa, active,
-                     gy, ldg, aligned(gy, ldg) ? 1 : 0, gv, ldgv, aligned(gv, ldgv) ? 1 : 0, old_mode,
+                     img->items, img->n_items, img->Wrow, p->n, v, B, ldv, rows_aligned16(v, ldv) ? 1 : 0, kappa, active,
+                     gy, ldg, rows_aligned16(gy, ldg) ? 1 : 0, gv, ldgv, rows_aligned16(gv, ldgv) ? 1 : 0, old_mode,
                      static_cast<const int32_t*>(nullptr), 0);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }

@@ -296,11 +296,7 @@ int mfma64_bwd_build(const RayenPack* p, Mfma64BwdImage** out, int64_t* bytes) {
   img->nkk = np / 32;
   img->n_items = n_real;
   const std::vector<int32_t> seg_bucket = bucket_table(p, bwd_quad_like, &img->n_dense);
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   const bool ok =
       hipMalloc(&img->S, frag.size() * sizeof(double)) == hipSuccess &&
       hipMemcpy(img->S, frag.data(), frag.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
@@ -334,9 +330,7 @@ static int launch_bwd64(const RayenPack* p, const Mfma64BwdImage* img, const dou
   int32_t* ws = static_cast<int32_t*>(workspace);
   if (bucketed) launch_bucket_sort<double>(kappa, active, B, img->seg_bucket, nb, ws, stream);
   const int64_t n_groups = bucketed ? (B + 31) / 32 + 2 * nb : (B + 31) / 32;   // (bucketed: the kernel reads the true count)
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kB64Waves - 1) / kB64Waves;
+  const int64_t grid = grid_for_groups(n_groups, slots, kB64Waves);
   if (bucketed)
     hipLaunchKernelGGL((mfma64_bwd_kernel<NKK, true>), dim3((unsigned)grid), dim3(kB64Waves * 64), 0, stream, img->S,
                        img->items, img->n_items, img->Wrow, p->n, v, B, ldv, kappa, active, gy, ldg, gv, ldgv, 0,

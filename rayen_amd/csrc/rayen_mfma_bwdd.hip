@@ -463,11 +463,7 @@ int mfma_bwdd_build(const RayenPack* p, MfmaBwddImage** out, int64_t* bytes) {
     if (g.type == RAYEN_SEG_LIN) { lo = std::min(lo, (int)g.row0); hi = std::max(hi, (int)(g.row0 + g.nrows)); }
   img->lin_lo = hi > lo ? lo : 0;
   img->lin_n = hi > lo ? hi - lo : 0;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   auto lds_of = [&](int lin_n) { return n_tiles * 8192 + lin_n * 256 + img->n_dense * 512 + kBdWaves * kBdStage + 16 + img->n_dense * 16; };
   if (lds_of(img->lin_n) > 160 * 1024) img->lin_n = 0;      // (the linear rows stay in L2: gathered from there)
   img->lds_bytes = lds_of(img->lin_n);
@@ -507,8 +503,7 @@ bool mfma_bwdd_serves(const RayenPack* p, const MfmaBwddImage* img, const float*
                       const float* gy, int64_t ldg, const float* gv, int64_t ldgv) {
   (void)p;
   if (img == nullptr || !img->ready) return false;
-  auto aligned = [](const void* ptr, int64_t ld) { return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0); };
-  if (!aligned(v, ldv) || !aligned(gy, ldg) || !aligned(gv, ldgv)) return false;
+  if (!rows_aligned16(v, ldv) || !rows_aligned16(gy, ldg) || !rows_aligned16(gv, ldgv)) return false;
   // (buffer addressing with 32-bit byte offsets; the rows of the ragged last group beyond the batch must not wrap)
   auto fits = [&](int64_t ld) { return (uint64_t)(B + 64) * (uint64_t)ld * 4u < (1ull << 32); };
   if (!fits(ldv) || !fits(ldg) || !fits(ldgv)) return false;

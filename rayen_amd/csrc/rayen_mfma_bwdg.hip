@@ -374,14 +374,6 @@ void mfma_bwdg_free(MfmaBwdgImage* img) {
   delete img;
 }
 
-template <typename T>
-static bool upload_vec(const std::vector<T>& host, T** dev, int64_t* bytes) {
-  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return false;
-  if (hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
-  *bytes += (int64_t)(host.size() * sizeof(T));
-  return true;
-}
-
 int mfma_bwdg_build(const RayenPack* p, MfmaBwdgImage** out, int64_t* bytes) {
   const int n = p->n, k = p->k, np = n_pad_of(n), nkk = np / 32;
   const double* W = p->W.data();
@@ -402,11 +394,7 @@ int mfma_bwdg_build(const RayenPack* p, MfmaBwdgImage** out, int64_t* bytes) {
   img->nkk = nkk;
   img->nkg = p->out_identity ? 0 : n_pad_of(k) / 32;
   img->n_items = n_real;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   const std::vector<float> frag = b.fragments_f32();
   std::vector<float> wrow((size_t)(p->n_rows + 2) * np, 0.f);
   for (int r = 0; r < p->n_rows; ++r)
@@ -414,12 +402,12 @@ int mfma_bwdg_build(const RayenPack* p, MfmaBwdgImage** out, int64_t* bytes) {
   bool ok = true;
   {
     float* d = nullptr;
-    ok = ok && upload_vec(frag, &d, &img->bytes);
+    ok = ok && upload_to_device(frag, &d, &img->bytes);
     img->S = reinterpret_cast<f32x4*>(d);
   }
-  ok = ok && upload_vec(wrow, &img->Wrow, &img->bytes) && upload_vec(items, &img->items, &img->bytes) &&
-       upload_vec(packs, &img->packs, &img->bytes) && upload_vec(seg_aux, &img->seg_aux, &img->bytes) &&
-       upload_vec(seg_bucket, &img->seg_bucket, &img->bytes) && upload_vec(group_items, &img->group_items, &img->bytes);
+  ok = ok && upload_to_device(wrow, &img->Wrow, &img->bytes) && upload_to_device(items, &img->items, &img->bytes) &&
+       upload_to_device(packs, &img->packs, &img->bytes) && upload_to_device(seg_aux, &img->seg_aux, &img->bytes) &&
+       upload_to_device(seg_bucket, &img->seg_bucket, &img->bytes) && upload_to_device(group_items, &img->group_items, &img->bytes);
   if (ok && !p->out_identity) {
     // NA_E' : rows = the n subspace coordinates, K = the k ambient coordinates
     TileLayout bn(k);
@@ -433,7 +421,7 @@ int mfma_bwdg_build(const RayenPack* p, MfmaBwdgImage** out, int64_t* bytes) {
     }
     const std::vector<float> fn = bn.fragments_f32();
     float* d = nullptr;
-    ok = upload_vec(fn, &d, &img->bytes);
+    ok = upload_to_device(fn, &d, &img->bytes);
     img->NT = reinterpret_cast<f32x4*>(d);
   }
   if (!ok) { mfma_bwdg_free(img); return RAYEN_E_ALLOC; }
@@ -459,20 +447,17 @@ static int launch_bwdg(const RayenPack* p, const MfmaBwdgImage* img, const float
   if (bucketed) launch_bucket_sort<float>(kappa, active, B, img->seg_bucket, nb, ws, stream);
   const int64_t n_groups = (B + per_wave - 1) / per_wave + (bucketed ? (64 / per_wave) * nb : 0);
   const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
-  auto aligned = [](const void* ptr, int64_t ld) { return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0); };
+  const int64_t grid = grid_for_groups(n_groups, slots, kMfmaWaves);
   if (bucketed)
     hipLaunchKernelGGL((mfma_bwdg_kernel<NKK, NKG, true>), dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream, img->S,
                        img->NT, img->items, img->n_items, img->packs, img->seg_aux, img->Wrow, p->n, p->k, v, B, ldv,
-                       aligned(v, ldv) ? 1 : 0, kappa, active, gy, ldg, aligned(gy, ldg) ? 1 : 0, gv, ldgv,
-                       aligned(gv, ldgv) ? 1 : 0, 0, static_cast<const int32_t*>(ws), nb, img->group_items);
+                       rows_aligned16(v, ldv) ? 1 : 0, kappa, active, gy, ldg, rows_aligned16(gy, ldg) ? 1 : 0, gv, ldgv,
+                       rows_aligned16(gv, ldgv) ? 1 : 0, 0, static_cast<const int32_t*>(ws), nb, img->group_items);
   else
     hipLaunchKernelGGL((mfma_bwdg_kernel<NKK, NKG, false>), dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream, img->S,
                        img->NT, img->items, img->n_items, img->packs, img->seg_aux, img->Wrow, p->n, p->k, v, B, ldv,
-                       aligned(v, ldv) ? 1 : 0, kappa, active, gy, ldg, aligned(gy, ldg) ? 1 : 0, gv, ldgv,
-                       aligned(gv, ldgv) ? 1 : 0, old_mode, static_cast<const int32_t*>(nullptr), 0,
+                       rows_aligned16(v, ldv) ? 1 : 0, kappa, active, gy, ldg, rows_aligned16(gy, ldg) ? 1 : 0, gv, ldgv,
+                       rows_aligned16(gv, ldgv) ? 1 : 0, old_mode, static_cast<const int32_t*>(nullptr), 0,
                        static_cast<const int32_t*>(nullptr));
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }

@@ -362,14 +362,6 @@ static std::vector<double> fragments_f64(const TileLayout& b) {
   return frag;
 }
 
-template <typename T>
-static bool upload64(const std::vector<T>& host, T** dev, int64_t* bytes) {
-  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return false;
-  if (hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
-  *bytes += (int64_t)(host.size() * sizeof(T));
-  return true;
-}
-
 int mfma64_bwdg_build(const RayenPack* p, Mfma64BwdgImage** out, int64_t* bytes) {
   const int n = p->n, k = p->k, np = n_pad_of(n);
   TileLayout b(n);
@@ -381,11 +373,7 @@ int mfma64_bwdg_build(const RayenPack* p, Mfma64BwdgImage** out, int64_t* bytes)
   Mfma64BwdgImage* img = new Mfma64BwdgImage();
   img->nkg = p->out_identity ? 0 : n_pad_of(k) / 32;
   img->n_items = n_real;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   const std::vector<double> frag = fragments_f64(b);
   std::vector<double> wrow((size_t)(p->n_rows + 2) * np, 0.0);
   for (int r = 0; r < p->n_rows; ++r)
@@ -393,11 +381,11 @@ int mfma64_bwdg_build(const RayenPack* p, Mfma64BwdgImage** out, int64_t* bytes)
   bool ok = true;
   {
     double* d = nullptr;
-    ok = ok && upload64(frag, &d, &img->bytes);
+    ok = ok && upload_to_device(frag, &d, &img->bytes);
     img->S = reinterpret_cast<f64x2*>(d);
   }
-  ok = ok && upload64(wrow, &img->Wrow, &img->bytes) && upload64(items, &img->items, &img->bytes) &&
-       upload64(packs, &img->packs, &img->bytes) && upload64(seg_aux, &img->seg_aux, &img->bytes);
+  ok = ok && upload_to_device(wrow, &img->Wrow, &img->bytes) && upload_to_device(items, &img->items, &img->bytes) &&
+       upload_to_device(packs, &img->packs, &img->bytes) && upload_to_device(seg_aux, &img->seg_aux, &img->bytes);
   if (ok && !p->out_identity) {
     TileLayout bn(k);  // NA_E': rows = the n subspace coordinates (one tile), K = the k ambient coordinates
     std::vector<std::vector<double>> nt(n, std::vector<double>(k, 0.0));
@@ -408,7 +396,7 @@ int mfma64_bwdg_build(const RayenPack* p, Mfma64BwdgImage** out, int64_t* bytes)
     bn.add_tile(rows, k);
     const std::vector<double> fn = fragments_f64(bn);
     double* d = nullptr;
-    ok = upload64(fn, &d, &img->bytes);
+    ok = upload_to_device(fn, &d, &img->bytes);
     img->NT = reinterpret_cast<f64x2*>(d);
   }
   if (!ok) { mfma64_bwdg_free(img); return RAYEN_E_ALLOC; }
@@ -423,9 +411,7 @@ static int launch_bwdg64(const RayenPack* p, const Mfma64BwdgImage* img, const d
                          int64_t ldgv, int old_mode, hipStream_t stream) {
   const int64_t n_groups = (B + 31) / 32;
   const int64_t slots = (int64_t)launch_simds(img->n_simd) * 2;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kG64Waves - 1) / kG64Waves;
+  const int64_t grid = grid_for_groups(n_groups, slots, kG64Waves);
   hipLaunchKernelGGL((mfma64_bwdg_kernel<NKG>), dim3((unsigned)grid), dim3(kG64Waves * 64), 0, stream, img->S,
                      img->NT, img->items, img->n_items, img->packs, img->seg_aux, img->Wrow, p->n, p->k, v, B, ldv,
                      kappa, active, gy, ldg, gv, ldgv, old_mode);

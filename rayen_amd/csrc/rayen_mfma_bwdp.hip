@@ -490,14 +490,6 @@ void mfma_bwdp_free(MfmaBwdpImage* img) {
 
 namespace {
 
-template <typename T>
-bool upload(const std::vector<T>& host, T** dev, int64_t* bytes) {
-  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return false;
-  if (hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
-  *bytes += (int64_t)(host.size() * sizeof(T));
-  return true;
-}
-
 // power of two that puts `big` into [2^13, 2^14)
 void pow2_for(const double big, float* scale, float* inv) {
   int ex = 0;
@@ -594,11 +586,7 @@ int mfma_bwdp_build(const RayenPack* p, MfmaBwdpImage** out, int64_t* bytes) {
   MfmaBwdpImage* img = new MfmaBwdpImage();
   img->nkg = p->out_identity ? 0 : n_pad_of(k) / 32;
   img->n_pairs = n_real / 2;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   std::vector<int32_t> seg_info((p->segs.size() + 1) * 4, 0);
   for (size_t sidx = 0; sidx <= p->segs.size(); ++sidx) seg_info[4 * sidx] = -1;
   for (int pr = 0; pr < img->n_pairs; ++pr)
@@ -626,11 +614,11 @@ int mfma_bwdp_build(const RayenPack* p, MfmaBwdpImage** out, int64_t* bytes) {
   bool ok = true;
   {
     _Float16* d = nullptr;
-    ok = ok && upload(uh, &d, &img->bytes);
+    ok = ok && upload_to_device(uh, &d, &img->bytes);
     img->U = reinterpret_cast<f16x8*>(d);
   }
-  ok = ok && upload(wrow, &img->Wrow, &img->bytes) && upload(seg_aux, &img->seg_aux, &img->bytes) &&
-       upload(seg_info, &img->seg_info, &img->bytes);
+  ok = ok && upload_to_device(wrow, &img->Wrow, &img->bytes) && upload_to_device(seg_aux, &img->seg_aux, &img->bytes) &&
+       upload_to_device(seg_info, &img->seg_info, &img->bytes);
   if (ok && !p->out_identity) {
     // NA_E' : rows = the n subspace coordinates, K = the k ambient coordinates
     TileLayout bn(k);
@@ -648,7 +636,7 @@ int mfma_bwdp_build(const RayenPack* p, MfmaBwdpImage** out, int64_t* bytes) {
     pow2_for(nbig, &n_scale, &img->n_inv);
     const std::vector<_Float16> nh = pair_chunks(bn, n_scale);
     _Float16* d = nullptr;
-    ok = upload(nh, &d, &img->bytes);
+    ok = upload_to_device(nh, &d, &img->bytes);
     img->NT = reinterpret_cast<f16x8*>(d);
   }
   if (!ok) { mfma_bwdp_free(img); return RAYEN_E_ALLOC; }
@@ -687,18 +675,13 @@ static int launch_bwdp(const RayenPack* p, const MfmaBwdpImage* img, const float
                        const float* kappa, const int32_t* active, const float* gy, int64_t ldg, float* gv,
                        int64_t ldgv, hipStream_t stream) {
   const int64_t n_groups = (B + 63) / 64;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
-  auto aligned = [](const void* ptr, int64_t ld) { return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0); };
-  auto base16 = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+  const int64_t grid = grid_for_groups(n_groups, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
   // rows of v, grad_v and grad_y stored back to back behind 16-byte aligned bases: whole 16-byte pieces of the group's blocks
-  const bool flat = ldv == p->n && ldgv == p->n && base16(v) && base16(gv) && ldg == p->k && base16(gy);
+  const bool flat = ldv == p->n && ldgv == p->n && base_aligned16(v) && base_aligned16(gv) && ldg == p->k && base_aligned16(gy);
   auto go = [&](auto kern, const unsigned lds) {
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), lds, stream, img->U, img->NT, img->n_pairs,
-                       img->seg_info, img->seg_aux, img->Wrow, p->n, p->k, v, B, ldv, aligned(v, ldv) ? 1 : 0, kappa, active,
-                       gy, ldg, aligned(gy, ldg) ? 1 : 0, gv, ldgv, aligned(gv, ldgv) ? 1 : 0, img->u_unscale,
+                       img->seg_info, img->seg_aux, img->Wrow, p->n, p->k, v, B, ldv, rows_aligned16(v, ldv) ? 1 : 0, kappa, active,
+                       gy, ldg, rows_aligned16(gy, ldg) ? 1 : 0, gv, ldgv, rows_aligned16(gv, ldgv) ? 1 : 0, img->u_unscale,
                        img->n_inv);
   };
   // (resident wherever the image fits: one copy per workgroup against one stream per wave and group)

@@ -405,11 +405,7 @@ int mfma64_build(const RayenPack* p, Mfma64Image** out, int64_t* bytes) {
   img->nkk = b.n_pad / 32;
   img->identity = p->out_identity;
   img->n_items = (int)b.items.size();
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   const int k_tiles = (p->k + 31) / 32;
   std::vector<double> y0((size_t)k_tiles * 32 + 32, 0.0);
   for (int i = 0; i < p->k; ++i) y0[i] = p->y0[i];
@@ -436,9 +432,7 @@ static int launch64(const RayenPack* p, const Mfma64Image* img, const double* v,
   // persistent, balanced: 2 waves per SIMD, every wave the same number of 32-sample groups
   const int64_t n_groups = (B + 31) / 32;
   const int64_t slots = (int64_t)launch_simds(img->n_simd) * 2;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + k64Waves - 1) / k64Waves;
+  const int64_t grid = grid_for_groups(n_groups, slots, k64Waves);
   if (active != nullptr) {
     hipLaunchKernelGGL((mfma64_fwd_kernel<NKK, true>), dim3((unsigned)grid), dim3(k64Waves * 64), 0, stream,
                        img->W, img->items, img->n_items, img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, y, ldy,

@@ -609,11 +609,9 @@ static int launch_mfma(const RayenPack* p, const MfmaImage* img, const float* v,
   constexpr int per_wave = MfmaCfg<NKK>::NT * 32;
   const int64_t n_groups = (B + per_wave - 1) / per_wave;
   const int64_t slots = (int64_t)launch_simds(img->n_simd) * img->waves_per_simd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
-  const int vec_in = (ldv % 4 == 0) && ((reinterpret_cast<uintptr_t>(v) & 15) == 0);
-  const int vec_out = (ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
+  const int64_t grid = grid_for_groups(n_groups, slots, kMfmaWaves);
+  const int vec_in = rows_aligned16(v, ldv);
+  const int vec_out = rows_aligned16(y, ldy);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream, img->W, img->items,
                        img->n_items, img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, vec_in, y, ldy,

@@ -16,7 +16,7 @@ int mfma_forward_mapped(const RayenPack* p, const MfmaImage* img, const float* x
                         int in_dim, const float* w, int64_t ldw, const float* bias, float* v_out,
                         int64_t ldvo, float* y, int64_t ldy, float* kappa, int32_t* active,
                         int32_t* nan_flag, hipStream_t stream) {
-  if (!mfma_mapper_fusable(p, img, in_dim) || ldw % 4 != 0 || (reinterpret_cast<uintptr_t>(w) & 15) != 0)
+  if (!mfma_mapper_fusable(p, img, in_dim) || ldw % 4 != 0 || !base_aligned16(w))
     return RAYEN_E_UNSUPPORTED;
   if (B == 0) return RAYEN_OK;
   MapperArgs mp;

@@ -607,196 +607,21 @@ __global__ __launch_bounds__(256) void pair_mapper_image_kernel(const float* __r
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-void mfma_pair_free(PairImage* img) {
-  if (img == nullptr) return;
-  if (img->Wh) (void)hipFree(img->Wh);
-  if (img->items) (void)hipFree(img->items);
-  if (img->packs) (void)hipFree(img->packs);
-  if (img->y0) (void)hipFree(img->y0);
-  delete img;
-}
-
-static int pair_build(const RayenPack* p, PairImage** out, int64_t* bytes, bool tri);
-int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes) {
-  // (RAYEN_PAIR_TRI=0: dense factors, two tiles each -- the image of rounds 3 and 4, for A/B measurements)
-  const char* tri_env = std::getenv("RAYEN_PAIR_TRI");
-  return pair_build(p, out, bytes, !(tri_env != nullptr && tri_env[0] == '0'));
-}
-bool mfma_pair_has_halves(const PairImage* img) { return img != nullptr && img->has_halves; }
-// the image of the instances behind the fused mapper: every item a full tile
-int mfma_pair_build_dense(const RayenPack* p, PairImage** out, int64_t* bytes) { return pair_build(p, out, bytes, false); }
-
-static int pair_build(const RayenPack* p, PairImage** out, int64_t* bytes, const bool tri) {
-  TileLayout b(p->n);
-  const int rc = layout_tiles(p, b, /*allow_pack=*/true, /*allow_sym=*/false, tri);
-  if (rc != RAYEN_OK) return rc;
-  if (b.packs.empty()) { MPack none; std::memset(&none, 0, sizeof(none)); b.packs.push_back(none); }
-  // an item also carries the NEXT item's tile and shape (in `qbegin`, which only symmetric-form layouts use): the walks
-  // need them in front of an item's burst, and a scalar load issued there would be waited for there
-  for (size_t i = 0; i < b.items.size(); ++i) b.items[i].qbegin = b.items[i + 1 < b.items.size() ? i + 1 : i].tile_shape;
-  // ---- one power of two per quadratic / cone on top of the image's gW (round 3).  f16 has five exponent bits: with ONE
-  // scale for the whole image, a constraint whose rows are 2^-15 of the image's largest entry keeps only its leading
-  // pieces (config 5's jerk limits next to its corridor rows: 3e-5 -- the creation-time measurement sent the set to the
-  // bf16 triples).  A candidate phi.v + ||U v|| is homogeneous in ITS OWN rows (aux rows and factor rows together), so
-  // every such segment's rows are boosted by f_s = 2^e_s into the band the image's largest entry sits in, and its
-  // candidate is multiplied by 1 / f_s (exact) before it meets the running maximum (MItem::seg_inv, MPack::inv).
-  // Linear rows keep the image's scale (their maximum runs over rows of different segments' worth of scale).
-  std::vector<float> seg_inv(p->segs.size(), 1.f);
-  {
-    // who owns an entry of the image: [tile row][column half] (a shared tile's rows belong to one segment in columns
-    // 0..31 and to another in columns 32..63, rayen_tiles.h)
-    const int n_tiles0 = b.n_tiles();
-    const int half_w = b.n_pad >= 64 ? 32 : b.n_pad;
-    std::vector<int> cell_seg((size_t)n_tiles0 * 32 * 2, -1);
-    auto own_row = [&](int tile, int r, int shape, int seg) {
-      if (shape != MS_HALF_B) cell_seg[((size_t)tile * 32 + r) * 2 + 0] = seg;
-      if (shape != MS_HALF_A) cell_seg[((size_t)tile * 32 + r) * 2 + 1] = seg;
-    };
-    int cur_aux = -1;
-    for (size_t idx = 0; idx < b.items.size(); ++idx) {
-      const MItem& it = b.items[idx];
-      if (it.type == MI_AUX) cur_aux = it.tile();
-      if (it.type == MI_QFAC || it.type == MI_SOC) {
-        for (int r = 0; r < 32; ++r) own_row(it.tile(), r, it.shape(), it.seg);
-        if (cur_aux >= 0) {
-          own_row(cur_aux, it.aux, MS_FULL, it.seg);
-          if (it.type == MI_SOC) own_row(cur_aux, it.aux + 1, MS_FULL, it.seg);
-        }
-      }
-      if (it.type == MI_PACK) {
-        const MPack& pk = b.packs[it.aux];
-        for (int a = 0; a < 4; ++a)
-          for (int h = 0; h < 2; ++h) {
-            if (pk.seg[a][h] < 0) continue;
-            for (int c = 0; c < 4; ++c) own_row(it.tile(), 8 * a + 4 * h + c, MS_FULL, pk.seg[a][h]);
-            if (cur_aux >= 0) own_row(cur_aux, pk.aux[a][h], MS_FULL, pk.seg[a][h]);
-          }
-      }
-    }
-    auto cell_of = [&](size_t r, int c) { return cell_seg[r * 2 + (c >= half_w ? 1 : 0)]; };
-    double image_big = 0.0;
-    std::vector<double> seg_big(p->segs.size(), 0.0);
-    for (size_t r = 0; r < (size_t)n_tiles0 * 32; ++r)
-      for (int c = 0; c < b.n_pad; ++c) {
-        const double x = std::fabs(b.raw[r * b.n_pad + c]);
-        if (!std::isfinite(x)) continue;
-        image_big = x > image_big ? x : image_big;
-        const int sg = cell_of(r, c);
-        if (sg >= 0 && x > seg_big[sg]) seg_big[sg] = x;
-      }
-    std::vector<double> boost(p->segs.size(), 1.0);
-    for (size_t s = 0; s < p->segs.size(); ++s) {
-      if (!(seg_big[s] > 0.0) || !(image_big > 0.0)) continue;
-      int ex_seg = 0, ex_img = 0;
-      (void)std::frexp(seg_big[s], &ex_seg);
-      (void)std::frexp(image_big, &ex_img);
-      int e = ex_img - ex_seg;                    // the segment's largest entry into the binade of the image's
-      e = e < 0 ? 0 : (e > 60 ? 60 : e);
-      boost[s] = std::ldexp(1.0, e);
-      seg_inv[s] = (float)std::ldexp(1.0, -e);
-    }
-    for (size_t r = 0; r < (size_t)n_tiles0 * 32; ++r)
-      for (int c = 0; c < b.n_pad; ++c) {
-        const int sg = cell_of(r, c);
-        if (sg >= 0 && boost[sg] != 1.0) b.raw[r * b.n_pad + c] *= boost[sg];
-      }
-    for (MItem& it : b.items)
-      if (it.type == MI_QFAC || it.type == MI_SOC) it.seg_inv = seg_inv[it.seg];
-    for (MPack& pk : b.packs)
-      for (int a = 0; a < 4; ++a)
-        for (int h = 0; h < 2; ++h) pk.inv[a][h] = pk.seg[a][h] >= 0 ? seg_inv[pk.seg[a][h]] : 1.f;
-  }
-  const std::vector<float> frag = b.fragments_f32();
-
-  PairImage* img = new PairImage();
-  img->nkk = b.n_pad / 32;
-  img->identity = p->out_identity;
-  img->n_items = (int)b.items.size();
-  img->host_items = b.items;
-  for (const MItem& it : b.items) img->has_halves = img->has_halves || it.shape() != MS_FULL;
-  for (const RayenSegment& g : p->segs) img->aux_rows += aux_rows_of(g);
-  img->first_out = img->n_items;
-  for (int i = img->n_items - 1; i >= 0; --i)
-    if (b.items[i].type == MI_OUT) img->first_out = i;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
-  // gW: the largest entry of the image into [2^13, 2^14)
-  float big = 0.f;
-  for (const float x : frag)
-    if (std::isfinite(x)) big = std::fmax(big, std::fabs(x));
-  int ex = 0;
-  if (big > 0.f) (void)std::frexp(big, &ex);   // big = f 2^ex, f in [0.5, 1)
-  int shift = big > 0.f ? 14 - ex : 0;
-  shift = shift > 100 ? 100 : (shift < -100 ? -100 : shift);   // (beyond: f16 overflow -> the self-check rejects the pack)
-  img->w_scale = std::ldexp(1.0f, shift);
-  img->w_inv = std::ldexp(1.0f, -shift);
-  // two f16 pieces of every scaled entry, in the fragment order of v_mfma_f32_32x32x16_f16 (the bf16 instruction's):
-  // chunk (tile, k-step s, piece) = 64 lanes x 8 elements, element i of lane l = column
-  // 16 s + 8 (i >> 2) + 4 (l >> 5) + (i & 3) of row l & 31 = entry [2 s + (i >> 2)][l][i & 3] of the fp32 image
-  const int n_tiles = b.n_tiles(), ns = b.nq() / 2;
-  img->n_tiles = n_tiles;
-  std::vector<_Float16> wh((size_t)n_tiles * ns * 2 * 64 * 8);
-  for (int t = 0; t < n_tiles; ++t)
-    for (int sp = 0; sp < ns; ++sp)
-      for (int l = 0; l < 64; ++l)
-        for (int i = 0; i < 8; ++i) {
-          const float x = frag[(((size_t)t * b.nq() + 2 * sp + (i >> 2)) * 64 + l) * 4 + (i & 3)] * img->w_scale;
-          const _Float16 h1 = (_Float16)x;                    // round to nearest even
-          const _Float16 h2 = (_Float16)(x - (float)h1);      // (exact difference)
-          const size_t base = (((size_t)t * ns + sp) * 2) * 64 * 8 + (size_t)l * 8 + i;
-          wh[base] = h1;
-          wh[base + 64 * 8] = h2;
-        }
-  const int k_tiles = (p->k + 31) / 32;
-  std::vector<float> y0((size_t)k_tiles * 32 + 32, 0.f);
-  for (int i = 0; i < p->k; ++i) y0[i] = (float)p->y0[i];
-  const bool ok =
-      hipMalloc(&img->Wh, wh.size() * 2) == hipSuccess &&
-      hipMemcpy(img->Wh, wh.data(), wh.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->y0, y0.size() * sizeof(float)) == hipSuccess &&
-      hipMemcpy(img->y0, y0.data(), y0.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->items, b.items.size() * sizeof(MItem)) == hipSuccess &&
-      hipMemcpy(img->items, b.items.data(), b.items.size() * sizeof(MItem), hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->packs, b.packs.size() * sizeof(MPack)) == hipSuccess &&
-      hipMemcpy(img->packs, b.packs.data(), b.packs.size() * sizeof(MPack), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { mfma_pair_free(img); return RAYEN_E_ALLOC; }
-  img->bytes = (int64_t)(wh.size() * 2 + y0.size() * sizeof(float) + b.items.size() * sizeof(MItem) +
-                         b.packs.size() * sizeof(MPack));
-  *bytes = img->bytes;
-  *out = img;
-  return RAYEN_OK;
-}
-
 template <int NKK, int NT>
 static int launch_pair(const RayenPack* p, const PairImage* img, const float* v, int64_t B, int64_t ldv,
                        float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
                        hipStream_t stream) {
   constexpr int per_wave = NT * 32;
-  const int64_t n_groups = (B + per_wave - 1) / per_wave;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
+  const int64_t grid = persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
   // bit 0: rows are 16-byte aligned | bit 1: rows are stored back to back and the base is 16-byte aligned
-  const int vec_in = (((ldv % 4 == 0) && ((reinterpret_cast<uintptr_t>(v) & 15) == 0)) ? 1 : 0) |
-                     ((ldv == p->n && (reinterpret_cast<uintptr_t>(v) & 15) == 0) ? 2 : 0);
-  const int vec_out = (ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream,
-                       static_cast<const f16x8*>(img->Wh), img->items, img->n_items, img->packs, img->y0,
-                       img->identity, p->k, p->n, v, B, ldv, vec_in, y, ldy, vec_out, kappa, active, nan_flag,
-                       img->w_scale, img->w_inv);
-  };
-  if (img->identity) {
-    if (active != nullptr) go(mfma_pair_fwd_kernel<NKK, true, false, NT>);
-    else go(mfma_pair_fwd_kernel<NKK, false, false, NT>);
-  } else {
-    if (active != nullptr) go(mfma_pair_fwd_kernel<NKK, true, true, NT>);
-    else go(mfma_pair_fwd_kernel<NKK, false, true, NT>);
-  }
+  const int vec_in = (rows_aligned16(v, ldv) ? 1 : 0) | ((ldv == p->n && base_aligned16(v)) ? 2 : 0);
+  const int vec_out = rows_aligned16(y, ldy);
+  dispatch_track_staged(active != nullptr, !img->identity, [&](auto track, auto staged) {
+    hipLaunchKernelGGL((mfma_pair_fwd_kernel<NKK, decltype(track)::value, decltype(staged)::value, NT>), dim3((unsigned)grid),
+                       dim3(kMfmaWaves * 64), 0, stream, static_cast<const f16x8*>(img->Wh), img->items, img->n_items,
+                       img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, vec_in, y, ldy, vec_out, kappa, active,
+                       nan_flag, img->w_scale, img->w_inv);
+  });
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 
@@ -822,26 +647,15 @@ static int launch_pair_map(const RayenPack* p, const PairImage* img, const float
                            const PairMapper& mp, float* y, int64_t ldy, float* kappa, int32_t* active,
                            int32_t* nan_flag, hipStream_t stream) {
   constexpr int per_wave = 64;
-  const int64_t n_groups = (B + per_wave - 1) / per_wave;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
-  const int vec_in = ((ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0)) ? 1 : 0;
-  const int vec_out = (ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream,
-                       static_cast<const f16x8*>(img->Wh), img->items, img->n_items, img->packs, img->y0,
-                       img->identity, p->k, p->n, x, B, ldx, vec_in, y, ldy, vec_out, kappa, active, nan_flag,
-                       img->w_scale, img->w_inv, mp);
-  };
-  if (img->identity) {
-    if (active != nullptr) go(mfma_pair_map_kernel<NKK, true, NKX>);
-    else go(mfma_pair_map_kernel<NKK, false, NKX>);
-  } else {
-    if (active != nullptr) go(mfma_pair_map_kernel<NKK, true, NKX, true>);
-    else go(mfma_pair_map_kernel<NKK, false, NKX, true>);
-  }
+  const int64_t grid = persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
+  const int vec_in = rows_aligned16(x, ldx);
+  const int vec_out = rows_aligned16(y, ldy);
+  dispatch_track_staged(active != nullptr, !img->identity, [&](auto track, auto staged) {
+    hipLaunchKernelGGL((mfma_pair_map_kernel<NKK, decltype(track)::value, NKX, decltype(staged)::value>), dim3((unsigned)grid),
+                       dim3(kMfmaWaves * 64), 0, stream, static_cast<const f16x8*>(img->Wh), img->items, img->n_items,
+                       img->packs, img->y0, img->identity, p->k, p->n, x, B, ldx, vec_in, y, ldy, vec_out, kappa, active,
+                       nan_flag, img->w_scale, img->w_inv, mp);
+  });
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 

@@ -1109,7 +1109,7 @@ static int pair_io_mode(const RayenPack* p, const PairImage* img, const float* v
   // batches that cannot give every resident wave a 64-row group are launch-latency work: rayen_mfma_pair.hip runs them with 32
   // rows per wave (nothing to trickle in a single short round)
   if ((B + 63) / 64 < (int64_t)img->n_simd * kMfmaWavesPerSimd) return 0;
-  if ((reinterpret_cast<uintptr_t>(v) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return 0;
+  if (!base_aligned16(v) || !base_aligned16(y)) return 0;
   if (img->identity && p->n == img->nkk * 32 && p->k == p->n && (ldv % 4) == 0 && (ldy % 4) == 0 &&
       ldv <= (1 << 22) && ldy <= (1 << 22) && !(img->nkk == 2 && img->aux_rows > IoGeom<2>::AUXR) &&
       img->n_items >= (img->nkk == 2 ? IoGeom<2>::NBLK : IoGeom<1>::NBLK))
@@ -1139,11 +1139,7 @@ static int launch_pair_io(const RayenPack* p, const PairImage* img, const float*
                           float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
                           hipStream_t stream) {
   constexpr int per_wave = 64;
-  const int64_t n_groups = (B + per_wave - 1) / per_wave;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
+  const int64_t grid = persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream,
                        static_cast<const f16x8*>(img->Wh), img->items, img->n_items, img->packs, img->y0,
@@ -1196,16 +1192,13 @@ int mfma_pair_io_forward(const RayenPack* p, const PairImage* img, const float* 
   if (mode == 0) return RAYEN_E_UNSUPPORTED;
   if (mode == 2) {
     constexpr int per_wave = 64;
-    const int64_t n_groups = (B + per_wave - 1) / per_wave;
-    const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-    const int64_t rounds = (n_groups + slots - 1) / slots;
-    const int64_t waves = (n_groups + rounds - 1) / rounds;
-    const unsigned grid = (unsigned)((waves + kMfmaWaves - 1) / kMfmaWaves);
-    if (img->identity)
-      return active != nullptr ? launch_pair_iof_one<true, false>(p, img, v, B, y, kappa, active, nan_flag, grid, stream)
-                               : launch_pair_iof_one<false, false>(p, img, v, B, y, kappa, active, nan_flag, grid, stream);
-    return active != nullptr ? launch_pair_iof_one<true, true>(p, img, v, B, y, kappa, active, nan_flag, grid, stream)
-                             : launch_pair_iof_one<false, true>(p, img, v, B, y, kappa, active, nan_flag, grid, stream);
+    const unsigned grid =
+        (unsigned)persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
+    int rc = RAYEN_OK;
+    dispatch_track_staged(active != nullptr, !img->identity, [&](auto track, auto staged) {
+      rc = launch_pair_iof_one<decltype(track)::value, decltype(staged)::value>(p, img, v, B, y, kappa, active, nan_flag, grid, stream);
+    });
+    return rc;
   }
   if (img->nkk == 1) return launch_pair_io<1>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
   return launch_pair_io<2>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);

@@ -728,7 +728,7 @@ bool mfma_pair_wl_serves(const RayenPack* p, const PairImage* img, const float* 
   if ((ldv % 4) != 0 || (ldy % 4) != 0) return false;
   // (buffer addressing with 32-bit byte offsets: mfma_pair_wl_forward cuts a batch beyond 4 GiB of rows into several launches)
   if (ldv > (1 << 22) || ldy > (1 << 22)) return false;
-  if ((reinterpret_cast<uintptr_t>(v) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return false;
+  if (!base_aligned16(v) || !base_aligned16(y)) return false;
   if (img->nkk == 2 && img->aux_rows > WlGeom<2>::AUXR) return false;
   if (pair_wl_lds_bytes(img) > 160 * 1024) return false;
   // Every batch size (round 6, gpurun_out/r06zzd, r06zze; config 3, us per call): the grid is one workgroup per CU as soon as there is
@@ -786,8 +786,8 @@ bool mfma_pair_wl_serves_mapped(const RayenPack* p, const PairImage* img, const 
   if (!img->identity || p->k != p->n || p->n > img->nkk * 32 || p->n <= (img->nkk - 1) * 32 || (p->n % 4) != 0) return false;
   if (in_dim < 4 || in_dim > img->nkk * 32 || (in_dim % 4) != 0 || ldx < in_dim || ldy < p->n) return false;
   if ((ldx % 4) != 0 || (ldy % 4) != 0 || ldx > (1 << 22) || ldy > (1 << 22)) return false;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return false;
-  if (v_out != nullptr && ((ldvo % 4) != 0 || ldvo < p->n || ldvo > (1 << 22) || (reinterpret_cast<uintptr_t>(v_out) & 15) != 0)) return false;
+  if (!base_aligned16(x) || !base_aligned16(y)) return false;
+  if (v_out != nullptr && ((ldvo % 4) != 0 || ldvo < p->n || ldvo > (1 << 22) || !base_aligned16(v_out))) return false;
   if (img->nkk == 2 && img->aux_rows > WlGeom<2, true>::AUXR) return false;
   if (pair_wl_lds_bytes_mapped(img, (in_dim + 31) / 32) > 160 * 1024) return false;
   static const int64_t min_groups_env = [] { const char* e = getenv("RAYEN_WL_MIN_GROUPS"); return e ? atoll(e) : 1ll; }();   // developer sweeps

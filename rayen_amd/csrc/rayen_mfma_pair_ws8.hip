@@ -635,7 +635,7 @@ int mfma_pair_ws8_build(const RayenPack* p, const PairImage* img, Ws8Image** out
 bool mfma_pair_ws8_serves(const RayenPack* p, const PairImage* img, const Ws8Image* ws, const float* v, int64_t B,
                           int64_t ldv, const float* y, int64_t ldy) {
   if (ws == nullptr || img == nullptr) return false;
-  if ((reinterpret_cast<uintptr_t>(v) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return false;
+  if (!base_aligned16(v) || !base_aligned16(y)) return false;
   if ((ldv % 4) != 0 || (ldy % 4) != 0 || ldv < p->n || ldy < p->k || ldv > (1 << 22) || ldy > (1 << 22)) return false;
   // every workgroup (one per CU) gets at least two groups: below that there is nothing to overlap
   return (B + 63) / 64 >= (int64_t)(img->n_simd / 4) * 2;
@@ -644,10 +644,8 @@ bool mfma_pair_ws8_serves(const RayenPack* p, const PairImage* img, const Ws8Ima
 template <int NKK, int TPW>
 static int launch_ws8(const RayenPack* p, const PairImage* img, const Ws8Image* ws, const float* v, int64_t B, int64_t ldv,
                       float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream) {
-  const int64_t n_groups = (B + 63) / 64;
-  const int64_t cus = launch_simds(img->n_simd) / 4;
-  const int64_t rounds = (n_groups + cus - 1) / cus;
-  const unsigned grid = (unsigned)((n_groups + rounds - 1) / rounds);
+  // one workgroup per group and round, the workgroups dealt over the CUs in equal rounds
+  const unsigned grid = (unsigned)persistent_grid(B, 64, launch_simds(img->n_simd) / 4, 1);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kW8Waves * 64), 0, stream, static_cast<const f16x8*>(img->Wh), ws->items,
                        ws->items2, ws->tiles, img->packs, img->y0, v, B, ldv, y, ldy, kappa, active, nan_flag, img->w_scale, img->w_inv);

@@ -616,11 +616,7 @@ int mfma_split_build(const RayenPack* p, SplitImage** out, int64_t* bytes) {
   img->identity = p->out_identity;
   img->n_items = n_items;
 
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
-      img->n_simd = prop.multiProcessorCount * 4;
-  }
+  img->n_simd = device_simds(p->device, img->n_simd);
   // three bf16 pieces of every entry, in the fragment order of v_mfma_f32_32x32x16_bf16:
   // chunk (tile, k-step s, piece) = 64 lanes x 8 elements, element i of lane l = column
   // 16 s + 8 (i >> 2) + 4 (l >> 5) + (i & 3) of row l & 31 = entry [2 s + (i >> 2)][l][i & 3] of the fp32 image
@@ -653,21 +649,10 @@ int mfma_split_build(const RayenPack* p, SplitImage** out, int64_t* bytes) {
           wb[base + 64 * 8] = h2;
           wb[base + 2 * 64 * 8] = h3;
         }
-  const int k_tiles = (p->k + 31) / 32;
-  std::vector<float> y0((size_t)k_tiles * 32 + 32, 0.f);
-  for (int i = 0; i < p->k; ++i) y0[i] = (float)p->y0[i];
-  const bool ok =
-      hipMalloc(&img->Wb, wb.size() * 2) == hipSuccess &&
-      hipMemcpy(img->Wb, wb.data(), wb.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->y0, y0.size() * sizeof(float)) == hipSuccess &&
-      hipMemcpy(img->y0, y0.data(), y0.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->items, b.items.size() * sizeof(MItem)) == hipSuccess &&
-      hipMemcpy(img->items, b.items.data(), b.items.size() * sizeof(MItem), hipMemcpyHostToDevice) == hipSuccess &&
-      hipMalloc(&img->packs, b.packs.size() * sizeof(MPack)) == hipSuccess &&
-      hipMemcpy(img->packs, b.packs.data(), b.packs.size() * sizeof(MPack), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { mfma_split_free(img); return RAYEN_E_ALLOC; }
-  img->bytes = (int64_t)(wb.size() * 2 + y0.size() * sizeof(float) + b.items.size() * sizeof(MItem) +
-                         b.packs.size() * sizeof(MPack));
+  if (!upload_walk_image(p, b, wb, &img->Wb, &img->y0, &img->items, &img->packs, &img->bytes)) {
+    mfma_split_free(img);
+    return RAYEN_E_ALLOC;
+  }
   *bytes = img->bytes;
   *out = img;
   return RAYEN_OK;
@@ -678,27 +663,16 @@ static int launch_split(const RayenPack* p, const SplitImage* img, const float* 
                         float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
                         hipStream_t stream) {
   constexpr int per_wave = 64;
-  const int64_t n_groups = (B + per_wave - 1) / per_wave;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
+  const int64_t grid = persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
   // bit 0: rows are 16-byte aligned (float4 pieces of a row) | bit 1: rows are stored back to back and the base is 16-byte aligned
-  const int vec_in = (((ldv % 4 == 0) && ((reinterpret_cast<uintptr_t>(v) & 15) == 0)) ? 1 : 0) |
-                     ((ldv == p->n && (reinterpret_cast<uintptr_t>(v) & 15) == 0) ? 2 : 0);
-  const int vec_out = (ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream,
-                       static_cast<const bf16x8*>(img->Wb), img->items, img->n_items, img->packs, img->y0,
-                       img->identity, p->k, p->n, v, B, ldv, vec_in, y, ldy, vec_out, kappa, active, nan_flag);
-  };
-  if (img->identity) {
-    if (active != nullptr) go(mfma_split_fwd_kernel<NKK, true, false>);
-    else go(mfma_split_fwd_kernel<NKK, false, false>);
-  } else {
-    if (active != nullptr) go(mfma_split_fwd_kernel<NKK, true, true>);
-    else go(mfma_split_fwd_kernel<NKK, false, true>);
-  }
+  const int vec_in = (rows_aligned16(v, ldv) ? 1 : 0) | ((ldv == p->n && base_aligned16(v)) ? 2 : 0);
+  const int vec_out = rows_aligned16(y, ldy);
+  dispatch_track_staged(active != nullptr, !img->identity, [&](auto track, auto staged) {
+    hipLaunchKernelGGL((mfma_split_fwd_kernel<NKK, decltype(track)::value, decltype(staged)::value>), dim3((unsigned)grid),
+                       dim3(kMfmaWaves * 64), 0, stream, static_cast<const bf16x8*>(img->Wb), img->items, img->n_items,
+                       img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, vec_in, y, ldy, vec_out, kappa, active,
+                       nan_flag);
+  });
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 
@@ -727,25 +701,15 @@ static int launch_split_map(const RayenPack* p, const SplitImage* img, const flo
                             const SplitMapper& mp, float* y, int64_t ldy, float* kappa, int32_t* active,
                             int32_t* nan_flag, hipStream_t stream) {
   constexpr int per_wave = 64;
-  const int64_t n_groups = (B + per_wave - 1) / per_wave;
-  const int64_t slots = (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd;
-  const int64_t rounds = (n_groups + slots - 1) / slots;
-  const int64_t waves = (n_groups + rounds - 1) / rounds;
-  const int64_t grid = (waves + kMfmaWaves - 1) / kMfmaWaves;
-  const int vec_in = ((ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0)) ? 1 : 0;
-  const int vec_out = (ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kMfmaWaves * 64), 0, stream,
-                       static_cast<const bf16x8*>(img->Wb), img->items, img->n_items, img->packs, img->y0,
-                       img->identity, p->k, p->n, x, B, ldx, vec_in, y, ldy, vec_out, kappa, active, nan_flag, mp);
-  };
-  if (img->identity) {
-    if (active != nullptr) go(mfma_split_map_kernel<NKK, true, false, NKX>);
-    else go(mfma_split_map_kernel<NKK, false, false, NKX>);
-  } else {
-    if (active != nullptr) go(mfma_split_map_kernel<NKK, true, true, NKX>);
-    else go(mfma_split_map_kernel<NKK, false, true, NKX>);
-  }
+  const int64_t grid = persistent_grid(B, per_wave, (int64_t)launch_simds(img->n_simd) * kMfmaWavesPerSimd, kMfmaWaves);
+  const int vec_in = rows_aligned16(x, ldx);
+  const int vec_out = rows_aligned16(y, ldy);
+  dispatch_track_staged(active != nullptr, !img->identity, [&](auto track, auto staged) {
+    hipLaunchKernelGGL((mfma_split_map_kernel<NKK, decltype(track)::value, decltype(staged)::value, NKX>), dim3((unsigned)grid),
+                       dim3(kMfmaWaves * 64), 0, stream, static_cast<const bf16x8*>(img->Wb), img->items, img->n_items,
+                       img->packs, img->y0, img->identity, p->k, p->n, x, B, ldx, vec_in, y, ldy, vec_out, kappa, active,
+                       nan_flag, mp);
+  });
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 

@@ -1,0 +1,51 @@
+// The device image every schedule of the f16-pair forward reads (rayen_mfma_pair.hip, rayen_mfma_pair_io.hip,
+// rayen_mfma_pair_ws8.hip, rayen_mfma_pair_wl.hip), its host functions and the choice of the schedule that serves a call
+// (rayen_pair_image.hip).  Host code only: no kernel, no vector type.
+#pragma once
+
+#include <atomic>
+
+#include "rayen_tiles.h"
+
+namespace rayen {
+
+// two f16 pieces of every entry of gW W (gW a power of two), in the fragment order of v_mfma_f32_32x32x16_f16
+struct PairImage {
+  void* Wh = nullptr;      // [n_tiles][NS][2][64] x 8 f16
+  MItem* items = nullptr;
+  MPack* packs = nullptr;
+  float* y0 = nullptr;
+  int n_items = 0;
+  int nkk = 0;
+  int identity = 0;
+  int n_simd = 1024;
+  float w_scale = 1.f, w_inv = 1.f;
+  int aux_rows = 0;        // aux rows (phi | c, M'beta) of the whole set
+  int first_out = 0;       // index of the first NA_E tile in the item list (n_items when NA_E = I)
+  bool has_halves = false; // some items read half of a shared tile (rayen_tiles.h): not for the mapped instances
+  int n_tiles = 0;         // tiles of the image (rayen_mfma_pair_wl.hip copies all of them into LDS)
+  bool wl_ready = false;          // the W-in-LDS kernels were promised their dynamic LDS at pack creation
+  bool wl_mapped_ready = false;   // ... and their mapped instances (room for the widest mapper next to the image)
+  int64_t bytes = 0;
+  std::vector<MItem> host_items;   // the item list as uploaded (rayen_mfma_pair_ws8.hip deals it out to eight waves)
+};
+
+// eligibility is mfma_split_eligible's
+int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes);
+int mfma_pair_build_dense(const RayenPack* p, PairImage** out, int64_t* bytes);   // without shared tiles (fused mapper)
+bool mfma_pair_has_halves(const PairImage* img);
+void mfma_pair_free(PairImage* img);
+
+// the schedule in force (RAYEN_PAIR_IO at start-up, rayen_pair_schedule afterwards); modes: rayen_pair_image.hip
+std::atomic<int>& pair_schedule_cell();
+int pair_schedule();
+
+// One forward call on a pack the f16-pair kernels serve (p->pr32_state == 1), by the schedule in force.  *served: the
+// RAYEN_KERNEL_* family that took it (the mapped twin leaves it alone where the plain kernel serves the call).
+int mfma_pair_family_forward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy, float* kappa,
+                             int32_t* active, int32_t* nan_flag, hipStream_t stream, int* served);
+int mfma_pair_family_forward_mapped(const RayenPack* p, const float* x, int64_t B, int64_t ldx, int in_dim, const void* image,
+                                    float* v_out, int64_t ldvo, float* y, int64_t ldy, float* kappa, int32_t* active,
+                                    int32_t* nan_flag, hipStream_t stream, int* served);
+
+}  // namespace rayen

@@ -1,8 +1,10 @@
-// Vector types and the device image of the split-operand forward kernel (rayen_mfma_split.hip): three bf16 pieces of
-// every entry of W in MFMA fragment order + the item list.
+// Vector types and device helpers of the split-operand forward kernels, and the device image of the bf16-triple one
+// (rayen_mfma_split.hip): three bf16 pieces of every entry of W in MFMA fragment order + the item list.  The f16-pair
+// kernels' image is rayen_pair_image.h (included here: every kernel file of the family includes this header).
 #pragma once
 
 #include "rayen_mfma_kernel.h"
+#include "rayen_pair_image.h"
 
 namespace rayen {
 
@@ -230,27 +232,6 @@ struct SplitImage {
   int identity = 0;
   int n_simd = 1024;
   int64_t bytes = 0;
-};
-
-// rayen_mfma_pair.hip: two f16 pieces of every entry of gW W (gW a power of two), same fragment order
-struct PairImage {
-  void* Wh = nullptr;      // [n_tiles][NS][2][64] x 8 f16
-  MItem* items = nullptr;
-  MPack* packs = nullptr;
-  float* y0 = nullptr;
-  int n_items = 0;
-  int nkk = 0;
-  int identity = 0;
-  int n_simd = 1024;
-  float w_scale = 1.f, w_inv = 1.f;
-  int aux_rows = 0;        // aux rows (phi | c, M'beta) of the whole set
-  int first_out = 0;       // index of the first NA_E tile in the item list (n_items when NA_E = I)
-  bool has_halves = false; // some items read half of a shared tile (rayen_tiles.h): not for the mapped instances
-  int n_tiles = 0;         // tiles of the image (rayen_mfma_pair_wl.hip copies all of them into LDS)
-  bool wl_ready = false;          // the W-in-LDS kernels were promised their dynamic LDS at pack creation
-  bool wl_mapped_ready = false;   // ... and their mapped instances (room for the widest mapper next to the image)
-  int64_t bytes = 0;
-  std::vector<MItem> host_items;   // the item list as uploaded (rayen_mfma_pair_ws8.hip deals it out to eight waves)
 };
 
 }  // namespace rayen

@@ -94,6 +94,20 @@ struct TileLayout {
   }
 };
 
+// The device side the tile walks' images share (bf16 triples, f16 pairs): the operand chunks, y0 zero-padded to whole
+// tiles and one more, the item list and the packs.  Every pointer is set as soon as its allocation exists (the image's
+// free function releases them when a later step fails); *bytes = what now lives on the device.
+template <typename C>
+inline bool upload_walk_image(const RayenPack* p, const TileLayout& b, const std::vector<C>& chunks, void** W, float** y0,
+                              MItem** items, MPack** packs, int64_t* bytes) {
+  const int k_tiles = (p->k + 31) / 32;
+  std::vector<float> y0_host((size_t)k_tiles * 32 + 32, 0.f);
+  for (int i = 0; i < p->k; ++i) y0_host[i] = (float)p->y0[i];
+  *bytes = 0;
+  return upload_to_device(chunks, reinterpret_cast<C**>(W), bytes) && upload_to_device(y0_host, y0, bytes) &&
+         upload_to_device(b.items, items, bytes) && upload_to_device(b.packs, packs, bytes);
+}
+
 inline int aux_rows_of(const RayenSegment& g) {
   if (g.type == RAYEN_SEG_QUAD_SYM || g.type == RAYEN_SEG_QUAD_FAC) return 1;
   if (g.type == RAYEN_SEG_SOC) return 2;
