@@ -12,9 +12,11 @@
 //    exp(q - max) weights and |q| weights multiplied into G from LDS (ds_read_b128 rows of K coefficients);
 //  * per group: max and sum reduced across the L lanes, the vertex part scaled by exp(M_lane - M) / S lane-locally, the ray
 //    part added, ONE K-wide sum across the group; lane i then stores y[i], y[i + L], ... with yp added.
-// The backward recomputes lambda = exp(q - lse) from the forward's per-row log-sum-exp, forms g = G' grad_y column by
-// column (K FMAs per element of q) and writes grad_q = lambda (g - <lambda, g>) on the vertex columns and sign(q) g on
-// the ray columns, in the same 16-byte pieces.
+// The backward recomputes e = exp(q - lse) from the forward's per-row log-sum-exp and normalises it again,
+// lambda = e / sum(e): lse is stored rounded to the working precision, and exp turns that rounding (up to ulp(lse) / 2,
+// which grows with the logits) into a common relative error of every e -- the quotient cancels it exactly.  It forms
+// g = G' grad_y column by column (K FMAs per element of q) and writes grad_q = lambda (g - <lambda, g>) on the vertex
+// columns and sign(q) g on the ray columns, in the same 16-byte pieces.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -215,8 +217,9 @@ __global__ __launch_bounds__(kThreads) void bar_backward_kernel(const T* __restr
 #pragma unroll
     for (int i = 0; i < K; ++i) gy[i] = i < k ? grad_y[row * k + i] : T(0);
     const T lse = nv > 0 ? rowstat[row] : T(0);
-    T dot = T(0);
+    T dot = T(0), inv = T(0);            // <lambda, g> and 1 / sum_j exp(q_j - lse)
     if (nv > 0) {
+      T s = T(0);
       for (int p = li; p < pv; p += L) {
         T v[4];
         load4(qr + 4 * p, vec_in != 0, m - 4 * p, v);
@@ -228,11 +231,14 @@ __global__ __launch_bounds__(kThreads) void bar_backward_kernel(const T* __restr
             T gj = T(0);
 #pragma unroll
             for (int i = 0; i < K; ++i) gj = fma(g[i], gy[i], gj);
-            dot = fma(exp_(v[c] - lse), gj, dot);
+            const T e = exp_(v[c] - lse);
+            s += e;
+            dot = fma(e, gj, dot);
           }
         }
       }
-      dot = group_sum(dot, L);
+      inv = T(1) / group_sum(s, L);
+      dot = group_sum(dot, L) * inv;
     }
     T* __restrict__ gr = grad_q + row * ldq;
     for (int p = li; p < npieces; p += L) {
@@ -248,7 +254,7 @@ __global__ __launch_bounds__(kThreads) void bar_backward_kernel(const T* __restr
           for (int i = 0; i < K; ++i) gj = fma(g[i], gy[i], gj);
         }
         const T sgn = v[c] > T(0) ? T(1) : (v[c] < T(0) ? T(-1) : T(0));
-        o[c] = j < nv ? exp_(v[c] - lse) * (gj - dot) : sgn * gj;
+        o[c] = j < nv ? exp_(v[c] - lse) * inv * (gj - dot) : sgn * gj;
       }
       store4(gr + 4 * p, vec_out != 0, m - 4 * p, o);
     }

@@ -53,6 +53,17 @@ def _check_input(v, pack):
         raise RuntimeError("rayen_amd: input and constant pack live on different devices")
 
 
+def _dense_rows(t, width):
+    """``t`` with unit column stride and rows that do not overlap (row stride >= ``width``), copied only where it has
+    to be: ``row.expand(B, m)`` has row stride 0, and the one row of a ``[1, m]`` view may carry any stride.  The C ABI
+    keeps refusing a leading dimension below ``width``."""
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width):
+        return t.contiguous()
+    if t.shape[0] == 1 and t.stride(0) < width:
+        return t.as_strided(t.shape, (t.shape[1], 1))        # one row: its stride addresses nothing
+    return t
+
+
 def _ptr(t):
     """Device address of a tensor as a plain int (ctypes converts it to ``void*``; building a ``c_void_p`` object per
     argument costs ~0.3 us each -- ten of them per call is a third of a small-batch forward's host time)."""
@@ -149,8 +160,7 @@ def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old
     _check_input(v, pack)
     if old_head and v.shape[1] < pack.consts.n + 1:
         raise RuntimeError(f"rayen_amd: RAYEN_old needs {pack.consts.n + 1} input columns, got {v.shape[1]}")
-    if v.stride(1) != 1:
-        v = v.contiguous()
+    v = _dense_rows(v, pack.consts.n + (1 if old_head else 0))
     B = v.shape[0]
     k = pack.consts.k
     if out is not None:
@@ -206,8 +216,7 @@ def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=F
     scratch buffer it asks for (``rayen_bwd_workspace_bytes_f32``) so that it may group the samples by active
     constraint and walk only that constraint's tiles; ``False`` pins the plain walk (same results)."""
     _check_input(v, pack)
-    if v.stride(1) != 1:
-        v = v.contiguous()
+    v = _dense_rows(v, pack.consts.n + (1 if old_head else 0))
     grad_y = grad_y.contiguous()
     B = v.shape[0]
     # the kernels write the first n (+1 for the old head) columns of every row; wider inputs keep zeros
@@ -463,8 +472,7 @@ def bar_forward_raw(q, pack, want_rowstat=True):
     """``(y [B, k], rowstat [B] | None)`` through ``rayen_bar_forward_*``; ``rowstat`` is the per-row log-sum-exp of
     the vertex logits (the backward's input)."""
     _bar_check(q, pack)
-    if q.stride(1) != 1:
-        q = q.contiguous()
+    q = _dense_rows(q, pack.width)
     B = q.shape[0]
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     rowstat = torch.empty((B,), dtype=q.dtype, device=q.device) if want_rowstat else None
@@ -479,7 +487,7 @@ def bar_forward_raw(q, pack, want_rowstat=True):
 def bar_backward_raw(q, rowstat, grad_y, pack):
     """``grad_q`` (same shape as ``q``; columns beyond ``nv + nr`` are zero) through ``rayen_bar_backward_*``."""
     _bar_check(q, pack)
-    q = q.contiguous()
+    q = _dense_rows(q, pack.width).contiguous()
     grad_y = grad_y.to(q.dtype).contiguous()
     rowstat = rowstat.contiguous()
     B = q.shape[0]

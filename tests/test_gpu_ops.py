@@ -41,6 +41,23 @@ def test_opcheck_ray_project_mapped(monkeypatch, family):
                           test_utils=("test_schema", "test_faketensor", "test_autograd_registration"))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("nv,nr", [(9, 4), (13, 0)])
+def test_opcheck_bar_project(nv, nr, dtype):
+    import numpy as np
+    rng = np.random.default_rng(nv)
+    k, m = 5, nv + nr
+    pack = ops.BarPack(rng.normal(size=(k, m)), rng.normal(size=k), nv, nr, 0)
+    pack_id = ops.register_pack(pack)
+    q = torch.empty(97, m + 2, device="cuda", dtype=dtype).uniform_(-3, 3).requires_grad_(True)
+    torch.library.opcheck(torch.ops.rayen_amd.bar_project.default, (q, pack_id),
+                          test_utils=("test_schema", "test_faketensor", "test_autograd_registration"))
+    y, rowstat = torch.ops.rayen_amd.bar_project(q.detach(), pack_id)
+    torch.library.opcheck(torch.ops.rayen_amd.bar_project_bwd.default, (q.detach(), rowstat, torch.randn_like(y), pack_id),
+                          test_utils=("test_schema", "test_faketensor"))
+    pack.close()
+
+
 @pytest.mark.parametrize("name", ["c3", "c4", "c5r"])
 def test_bitwise_reproducible(name):
     cs, layer = _layer(name, create_map=False)
