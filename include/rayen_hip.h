@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 9
+#define RAYEN_ABI_VERSION 10
 
 enum {
   RAYEN_OK = 0,
@@ -356,6 +356,46 @@ int rayen_bar_backward_f32(const RayenBarPack* pack, const float* q, int64_t ldq
                            const float* grad_y, int64_t B, float* grad_q, void* stream);
 int rayen_bar_backward_f64(const RayenBarPack* pack, const double* q, int64_t ldq, const double* rowstat,
                            const double* grad_y, int64_t B, double* grad_q, void* stream);
+
+/* ---- method='DC3' (ABI v10): the reference's completion + gradient-correction layer (rayen/constraint_module.py:265-336)
+ *
+ * With p = y[partial] (n values) and y[other] = c0 + C p (k - n values), T steps of
+ *     r = relu(A1e p - b1e),  g_i = 0.5 p'Pe_i p + qe_i'p + re_i,  grad = 2 A1e' r + sum_i 2 (Pe_i p + qe_i) relu(g_i),
+ *     s <- lr grad + momentum s (s = 0 at the start),  p <- p - s
+ * from p = q[:, :n].  The stop is batch-global: after every step the maximum over the WHOLE batch of the relu'd residuals is
+ * taken; the iteration stops at step t >= 1 when t >= max_steps or that maximum is < eps.  Every row takes the same number
+ * of steps, which the forward writes to *tstar (device memory, int32).
+ *
+ * A RayenDc3Pack holds fp32 and fp64 device images of A1e [m, n], b1e [m], Pe [nq, n, n], qe [nq, n], re [nq], C [k-n, n],
+ * c0 [k-n] (all fp64, row-major, read at creation) and of the index lists partial [n] / other [k-n]; immutable afterwards.
+ * The kernels keep one row per lane with n padded to 4, 8, 16, 32 or 64 (fp64: up to 32) and the image in LDS: n beyond
+ * that, or an image over 160 KiB ((m + nq (NP + 1) + (k - n)) NP elements plus padding), returns RAYEN_E_UNSUPPORTED from
+ * the forward and the backward (the pack is still created).
+ *
+ * forward: q [B, ldq] (first n columns read), y [B, ldy] (first k columns written).  ws: scratch of at least
+ *   rayen_dc3_workspace_bytes(pack, B, max_steps, f64, 0) bytes, 16-byte aligned; the steps run in launches of 32 with a
+ *   finishing launch (no host sync: capturable in a graph).  *nan_flag |= 1 where a y is NaN.
+ * backward: differentiates the *tstar steps the forward took (the stop decision carries no gradient, relu'(0) = 0);
+ *   grad_y [B, ldg], grad_q [B, ldgq] (first n columns written).  ws: at least rayen_dc3_workspace_bytes(.., 1) bytes, it
+ *   receives the recomputed trajectory [max_steps][n][B].  max_steps must be the forward's. */
+typedef struct RayenDc3Pack RayenDc3Pack;
+int rayen_dc3_pack_create(const double* A1e, const double* b1e, int32_t m, const double* Pe, const double* qe,
+                          const double* re, int32_t nq, const double* C, const double* c0, const int32_t* partial,
+                          const int32_t* other, int32_t n, int32_t k, RayenDc3Pack** out);
+void rayen_dc3_pack_destroy(RayenDc3Pack* pack);
+int64_t rayen_dc3_workspace_bytes(const RayenDc3Pack* pack, int64_t B, int32_t max_steps, int32_t f64, int32_t backward);
+int rayen_dc3_forward_f32(const RayenDc3Pack* pack, const float* q, int64_t B, int64_t ldq, float* y, int64_t ldy,
+                          double lr, double momentum, double eps, int32_t max_steps, int32_t* tstar, void* ws,
+                          int64_t ws_bytes, int32_t* nan_flag, void* stream);
+int rayen_dc3_forward_f64(const RayenDc3Pack* pack, const double* q, int64_t B, int64_t ldq, double* y, int64_t ldy,
+                          double lr, double momentum, double eps, int32_t max_steps, int32_t* tstar, void* ws,
+                          int64_t ws_bytes, int32_t* nan_flag, void* stream);
+int rayen_dc3_backward_f32(const RayenDc3Pack* pack, const float* q, int64_t B, int64_t ldq, const float* grad_y,
+                           int64_t ldg, float* grad_q, int64_t ldgq, double lr, double momentum, int32_t max_steps,
+                           const int32_t* tstar, void* ws, int64_t ws_bytes, void* stream);
+int rayen_dc3_backward_f64(const RayenDc3Pack* pack, const double* q, int64_t B, int64_t ldq, const double* grad_y,
+                           int64_t ldg, double* grad_q, int64_t ldgq, double lr, double momentum, int32_t max_steps,
+                           const int32_t* tstar, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,8 +18,10 @@ constants with plain torch ops on the caller's device (``rayen_amd/eager.py``; t
 ``'RAYEN_old'`` (:460-466) runs on the same kernels; ``'UU'`` is the identity and kept because it
 is free; ``'Bar'`` (the barycentric baseline, :124-132 and :479-486) converts the linear part of the set to
 vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kernel per direction
-(``rayen_amd/csrc/rayen_bar.hip``).  The other paper baselines (``UP, PP, DC3``) need solvers this package
-does not carry and raise ``NotImplementedError``.
+(``rayen_amd/csrc/rayen_bar.hip``); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
+quadratic sets only) needs ``args_DC3`` and runs its fixed iteration, batch-global stop included, on
+``rayen_amd/csrc/rayen_dc3.hip`` (host side: ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) need a conic
+solver inside the layer, which this package does not carry, and raise ``NotImplementedError``.
 
 Documented deviation: for an SOC whose ray never meets the cone (negative
 discriminant with ``c' < 0``) the reference's assert at :342 fires (or NaN under
@@ -35,7 +37,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, eager, ops, pack as _pack, utils
+from . import _lib, dc3 as _dc3, eager, ops, pack as _pack, utils
 
 
 class ConstraintModule(torch.nn.Module):
@@ -70,8 +72,12 @@ class ConstraintModule(torch.nn.Module):
         self.method = method
         if method == 'Bar' and cs.has_quadratic_constraints:
             raise Exception(f"Method {method} cannot be used with quadratic constraints")     # (:24-25)
-        if method not in ('RAYEN', 'RAYEN_old', 'UU', 'Bar'):
-            if method in ('UP', 'PP', 'DC3'):
+        if method == 'DC3':
+            if cs.has_soc_constraints or cs.has_lmi_constraints:
+                raise NotImplementedError("method 'DC3' serves linear and quadratic constraints only")     # (:27-28)
+            _dc3.check_args(args_DC3)        # (None: NotImplementedError, a RuntimeError like the reference's verify, :31)
+        elif method not in ('RAYEN', 'RAYEN_old', 'UU', 'Bar'):
+            if method in ('UP', 'PP'):
                 raise NotImplementedError(
                     f"method '{method}' is one of the reference's comparison baselines; rayen_amd "
                     "implements the RAYEN projection only")
@@ -147,9 +153,17 @@ class ConstraintModule(torch.nn.Module):
             assert (self.num_vertices + self.num_rays) > 0
             self._bar_packs = {}
 
+        if self.method == 'DC3':
+            _dc3.setup(self, cs)
+            self._dc3_packs = {}
+
         if self.method == 'RAYEN':
             self.forwardForMethod = self.forwardForRAYEN
             self.dim_after_map = self.n
+        elif self.method == 'DC3':
+            self.forwardForMethod = self.forwardForDC3
+            self.dim_after_map = self.k - self.neq_DC3
+            assert self.dim_after_map == self.n
         elif self.method == 'RAYEN_old':
             self.forwardForMethod = self.forwardForRAYENOld
             self.dim_after_map = self.n + 1
@@ -191,6 +205,7 @@ class ConstraintModule(torch.nn.Module):
         self.__dict__["_unsupported"] = set()
         self.__dict__.pop("_eager", None)
         self.__dict__["_bar_packs"] = {}
+        self.__dict__["_dc3_packs"] = {}
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -232,6 +247,8 @@ class ConstraintModule(torch.nn.Module):
         state["_unsupported"] = set()
         state.pop("_eager", None)
         state["_bar_packs"] = {}
+        state["_dc3_packs"] = {}
+        state.pop("dc3_steps", None)
         state.pop("forwardForMethod", None)
         return state
 
@@ -239,7 +256,8 @@ class ConstraintModule(torch.nn.Module):
         super().__setstate__(state)
         self._fast = {}
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
-                                 'UU': self.forwardForUU, 'Bar': self.forwardForBar}[self.method]
+                                 'UU': self.forwardForUU, 'Bar': self.forwardForBar,
+                                 'DC3': self.forwardForDC3}[self.method]
 
     # ------------------------------------------------------------------ the projection
     def _project(self, q, old_head=False):
@@ -356,6 +374,55 @@ class ConstraintModule(torch.nn.Module):
             return self._bar_reference(q2.unsqueeze(2))
         return y.unsqueeze(2)
 
+    # ------------------------------------------------------------------ method='DC3'
+    def dc3_pack(self, device):
+        """(pack, pack_id): the effective forms of the CURRENT buffers resident on ``device`` (built on first use;
+        forgotten by ``.to()`` and ``load_state_dict``)."""
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        packs = self.__dict__.setdefault("_dc3_packs", {})
+        entry = packs.get(index)
+        if entry is None:
+            dp = ops.Dc3Pack(_dc3.pack_arrays(self), index)
+            entry = packs[index] = (dp, ops.register_pack(dp))
+        return entry
+
+    def obtainyoFromypDC3(self, yp):
+        return self.A2oi @ (self.b2_DC3 - self.A2p @ yp)
+
+    def _dc3_reference(self, q):
+        """The reference iteration (:269-336) in plain torch ops on ``q``'s device and dtype; ``dc3_steps`` receives the
+        number of steps it took, as on the kernel path."""
+        y, steps = _dc3.reference_forward(self, q, return_steps=True)
+        self.__dict__["dc3_steps"] = torch.tensor([steps], dtype=torch.int32, device=q.device)
+        return y
+
+    def forwardForDC3(self, q):
+        if not q.is_cuda:
+            return self._dc3_reference(q)        # host tensors: the reference's formula, differentiable by autograd
+        q2 = torch.flatten(q, 1)
+        if q2.dtype not in (torch.float32, torch.float64):
+            return self.forwardForDC3(q2.float().unsqueeze(2)).to(q2.dtype)     # 16-bit activations: computed in fp32
+        if self._refused(q2):
+            return self._dc3_reference(q2.unsqueeze(2))
+        args = self.args_DC3
+        lr, momentum, eps = float(args['lr']), float(args['momentum']), float(args['eps_converge'])
+        limit = _dc3.max_steps(self)
+        try:
+            dp, pack_id = self.dc3_pack(q2.device)
+            if not (torch.is_grad_enabled() and q2.requires_grad) and not torch.compiler.is_compiling():
+                y, steps = ops.dc3_forward_raw(q2, dp, lr, momentum, eps, limit)      # plain inference: straight to the C ABI
+            else:
+                y, steps = torch.ops.rayen_amd.dc3_project(q2, pack_id, lr, momentum, eps, limit)
+        except _lib.RayenError as err:
+            if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
+                raise
+            warnings.warn(f"rayen_amd: no HIP kernel serves this DC3 layer ({err}); this module now runs the reference "
+                          "formula with torch ops on " + str(q2.device), RuntimeWarning, stacklevel=3)
+            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, False))
+            return self._dc3_reference(q2.unsqueeze(2))
+        self.__dict__["dc3_steps"] = steps      # [1] int32 on q's device: the steps this call took (every route sets it)
+        return y.unsqueeze(2)
+
     # ------------------------------------------------------------------ reference helper surface
     def getDimAfterMap(self):
         return self.dim_after_map
@@ -443,12 +510,16 @@ class ConstraintModule(torch.nn.Module):
             q = torch.unsqueeze(self.mapper(x2), dim=2)
             y = self.forwardForMethod(q)
 
-        if __debug__ and self.check_nan and self.method in ('RAYEN', 'RAYEN_old', 'Bar'):
+        if __debug__ and self.check_nan and self.method in ('RAYEN', 'RAYEN_old', 'Bar', 'DC3'):
+            what = "the projection produced NaN (NaN in the input?)"
+            if self.method == 'DC3':      # (the reference's words, CM:531)
+                what = f"If you are using DC3, try reducing args_DC3['lr']. Right now it's {self.args_DC3['lr']}"
             if not y.is_cuda or self._refused(y, self.method == 'RAYEN_old'):
-                assert not torch.isnan(y).any(), "the projection produced NaN (NaN in the input?)"     # CM:531
+                assert not torch.isnan(y).any(), what     # CM:531
             elif not torch.cuda.is_current_stream_capturing():  # the flag read is a host sync
-                dp, _ = self.bar_pack(y.device) if self.method == 'Bar' else self.device_pack(y.device)
+                dp, _ = (self.bar_pack(y.device) if self.method == 'Bar' else
+                         self.dc3_pack(y.device) if self.method == 'DC3' else self.device_pack(y.device))
                 if int(dp.nan_flag.item()) != 0:
                     dp.nan_flag.zero_()
-                    raise AssertionError("the projection produced NaN (NaN in the input?)")
+                    raise AssertionError(what)
         return y

@@ -535,3 +535,141 @@ def _bar_backward(ctx, grad_y, grad_rowstat):
 
 
 bar_project.register_autograd(_bar_backward, setup_context=_bar_setup_context)
+
+
+# ------------------------------------------------------------------------------------------------
+# method='DC3' (rayen/constraint_module.py:265-336): completion + T gradient-correction steps on rayen_dc3.hip
+# ------------------------------------------------------------------------------------------------
+
+# The backward keeps the recomputed trajectory [max_steps][n][B]; beyond this it refuses (train with fewer correction steps
+# or smaller batches: the reference's autograd graph holds several times as much).
+DC3_MAX_WORKSPACE_BYTES = 8 << 30
+
+
+class Dc3Pack:
+    """Owner of one ``RayenDc3Pack*``: fp32 and fp64 images of the effective forms (``rayen_amd/dc3.py::pack_arrays``) on one
+    device, plus the NaN flag its forward raises.  Immutable, so a captured graph may keep using it."""
+
+    def __init__(self, arrays, device_index):
+        a = arrays
+        self.n, self.k = int(a["n"]), int(a["k"])
+        self.device_index = int(device_index)
+        handle = ctypes.c_void_p()
+        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+        with torch.cuda.device(self.device_index):
+            _lib.check(_lib.load().rayen_dc3_pack_create(
+                ptr(a["A1e"]), ptr(a["b1e"]), int(a["A1e"].shape[0]), ptr(a["Pe"]), ptr(a["qe"]), ptr(a["re"]),
+                int(a["Pe"].shape[0]), ptr(a["C"]), ptr(a["c0"]), ptr(a["partial"]), ptr(a["other"]), self.n, self.k,
+                ctypes.byref(handle)), "rayen_dc3_pack_create")
+            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+        self.handle = handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.load().rayen_dc3_pack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _dc3_check(q, pack):
+    if not q.is_cuda:
+        raise RuntimeError("rayen_amd: the DC3 layer's HIP op runs on an MI355X (HIP) device only; got a "
+                           f"{q.device} tensor")
+    if q.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
+    if q.dim() != 2 or q.shape[1] < pack.n:
+        raise RuntimeError(f"rayen_amd: expected q of shape [B, >= {pack.n}], got {tuple(q.shape)}")
+    if q.device.index != pack.device_index:
+        raise RuntimeError("rayen_amd: input and DC3 pack live on different devices")
+
+
+def _dc3_workspace(pack, q, max_steps, backward):
+    nbytes = int(_lib.load().rayen_dc3_workspace_bytes(pack.handle, q.shape[0], int(max_steps),
+                                                       int(q.dtype == torch.float64), int(backward)))
+    if nbytes < 0:
+        raise RuntimeError("rayen_amd: rayen_dc3_workspace_bytes refused its arguments")
+    if nbytes > DC3_MAX_WORKSPACE_BYTES:
+        raise RuntimeError(f"rayen_amd: the DC3 {'backward' if backward else 'forward'} of {q.shape[0]} rows x {max_steps} "
+                           f"steps needs {nbytes} bytes of scratch, more than ops.DC3_MAX_WORKSPACE_BYTES = "
+                           f"{DC3_MAX_WORKSPACE_BYTES}; lower the step limit or split the batch")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device), nbytes
+
+
+def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
+    """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*``; ``steps`` is the batch-global number of steps."""
+    _dc3_check(q, pack)
+    q = _dense_rows(q, pack.n)
+    B = q.shape[0]
+    y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
+    steps = torch.empty((1,), dtype=torch.int32, device=q.device)
+    with _on_device(q.device):
+        ws, nbytes = _dc3_workspace(pack, q, max_steps, False)
+        code = _entry("rayen_dc3_forward_f32" if q.dtype == torch.float32 else "rayen_dc3_forward_f64")(
+            pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(y), pack.k, float(lr), float(momentum),
+            float(eps), int(max_steps), _ptr(steps), _ptr(ws), nbytes, _ptr(pack.nan_flag), _stream(q.device.index))
+    _lib.check(code, "rayen_dc3_forward")
+    return y, steps
+
+
+def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps):
+    """``grad_q`` (same shape as ``q``; columns beyond ``n`` are zero) through ``rayen_dc3_backward_*``."""
+    _dc3_check(q, pack)
+    q = _dense_rows(q, pack.n)
+    grad_y = grad_y.to(q.dtype).contiguous()
+    B = q.shape[0]
+    grad_q = torch.empty((B, q.shape[1]), dtype=q.dtype, device=q.device) if q.shape[1] == pack.n else \
+        torch.zeros((B, q.shape[1]), dtype=q.dtype, device=q.device)
+    with _on_device(q.device):
+        ws, nbytes = _dc3_workspace(pack, q, max_steps, True)
+        code = _entry("rayen_dc3_backward_f32" if q.dtype == torch.float32 else "rayen_dc3_backward_f64")(
+            pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(grad_y), pack.k, _ptr(grad_q),
+            grad_q.stride(0) if B else pack.n, float(lr), float(momentum), int(max_steps), _ptr(steps), _ptr(ws), nbytes,
+            _stream(q.device.index))
+    _lib.check(code, "rayen_dc3_backward")
+    return grad_q
+
+
+@torch.library.custom_op("rayen_amd::dc3_project", mutates_args=())
+def dc3_project(q: torch.Tensor, pack_id: int, lr: float, momentum: float, eps: float,
+                max_steps: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(y [B, k], steps [1] int32)``: the DC3 layer's forward on torch's current stream."""
+    return dc3_forward_raw(q, _pack(pack_id), lr, momentum, eps, max_steps)
+
+
+@dc3_project.register_fake
+def _(q, pack_id, lr, momentum, eps, max_steps):
+    pack = _pack(pack_id)
+    return q.new_empty((q.shape[0], pack.k)), q.new_empty((1,), dtype=torch.int32)
+
+
+@torch.library.custom_op("rayen_amd::dc3_project_bwd", mutates_args=())
+def dc3_project_bwd(q: torch.Tensor, steps: torch.Tensor, grad_y: torch.Tensor, pack_id: int, lr: float,
+                    momentum: float, max_steps: int) -> torch.Tensor:
+    return dc3_backward_raw(q, steps, grad_y, _pack(pack_id), lr, momentum, max_steps)
+
+
+@dc3_project_bwd.register_fake
+def _(q, steps, grad_y, pack_id, lr, momentum, max_steps):
+    return torch.empty_like(q)
+
+
+def _dc3_setup_context(ctx, inputs, output):
+    q, pack_id, lr, momentum, eps, max_steps = inputs
+    ctx.pack_id, ctx.lr, ctx.momentum, ctx.max_steps = pack_id, lr, momentum, max_steps
+    ctx.save_for_backward(q, output[1])
+
+
+def _dc3_backward(ctx, grad_y, grad_steps):
+    q, steps = ctx.saved_tensors
+    if grad_y is None:
+        return None, None, None, None, None, None
+    return (torch.ops.rayen_amd.dc3_project_bwd(q, steps, grad_y, ctx.pack_id, ctx.lr, ctx.momentum, ctx.max_steps),
+            None, None, None, None, None)
+
+
+dc3_project.register_autograd(_dc3_backward, setup_context=_dc3_setup_context)
