@@ -46,7 +46,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 32;                    // steps per launch
-constexpr size_t kLdsBudget = 160 * 1024;     // gfx950 LDS per CU (256 bytes of it are left to the kernels' static variables)
+constexpr size_t kLdsBudget = 160 * 1024;     // gfx950 LDS per CU (256 bytes of it are left to the kernels' static variables:
+                                              // sh_t today; -Rpass-analysis=kernel-resource-usage prints the figure)
 constexpr size_t kViolBytes = 8;              // one slot per step, wide enough for the bits of a double
 
 struct Dims {
@@ -243,10 +244,14 @@ __global__ __launch_bounds__(kThreads) void dc3_forward_kernel(const FwdArgs<T> 
   const bool record = chunk >= 0;
   if (record) {
     const int t0 = chunk * kChunk;
-    int stop = 0;
+    // (a vote through sh_t, not __syncthreads_or: that one brings 256 bytes of static LDS of its own, which with sh_t is
+    // more than kLdsBudget leaves beside the largest image)
+    if (threadIdx.x == 0) sh_t = 0;
+    __syncthreads();
     for (int t = 1 + (int)threadIdx.x; t <= t0; t += kThreads)
-      if (Bt::from(a.viol[t]) < a.eps) stop = 1;
-    if (__syncthreads_or(stop)) return;           // an earlier step already met the stop rule: write nothing
+      if (Bt::from(a.viol[t]) < a.eps) sh_t = 1;
+    __syncthreads();
+    if (sh_t) return;                             // an earlier step already met the stop rule: write nothing
     nsteps = a.max_steps - t0 < kChunk ? a.max_steps - t0 : kChunk;
   } else {
     if (threadIdx.x == 0) sh_t = a.max_steps;
@@ -384,13 +389,19 @@ __global__ __launch_bounds__(kThreads) void dc3_backward_kernel(const BwdArgs<T>
 #pragma unroll
     for (int j = 0; j < NP; ++j) w[j] = fma(crow[j], go, w[j]);
   }
+  // lr J(p_t)' sbar_t is summed on its own and added to pbar once per step: its m + nq n terms are small beside pbar, and
+  // adding them to pbar one by one costs each of them pbar's rounding (fp32, n = 64: 1e-5 of grad_q after 45 steps)
+  T dj[NP];
   for (int t = T_steps - 1; t >= 0; --t) {
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
       s[j] = a.momentum * s[j] - w[j];
       p[j] = j < d.n ? a.traj[((int64_t)t * d.n + j) * a.B + row] : T(0);
+      dj[j] = T(0);
     }
-    jacobian_transpose<T, NP>(L, d, p, s, a.lr, w);
+    jacobian_transpose<T, NP>(L, d, p, s, a.lr, dj);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) w[j] += dj[j];
   }
   T* __restrict__ gq = a.grad_q + row * a.ldgq;
 #pragma unroll
@@ -436,8 +447,10 @@ int launch_forward(const RayenDc3Pack* p, FwdArgs<T> a, hipStream_t stream) {
   auto kern = dc3_forward_kernel<T, NP>;
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
+          hipSuccess) {
+    (void)hipGetLastError();                      // (or the runtime's next caller finds this error waiting for it)
     return RAYEN_E_LAUNCH;
+  }
   const unsigned grid = (unsigned)((a.B + kThreads - 1) / kThreads);
   const int chunks = n_chunks(a.max_steps);
   for (int c = 0; c <= chunks; ++c) {
@@ -454,8 +467,10 @@ int launch_backward(const RayenDc3Pack* p, const BwdArgs<T>& a, hipStream_t stre
   auto kern = dc3_backward_kernel<T, NP>;
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
+          hipSuccess) {
+    (void)hipGetLastError();                      // (or the runtime's next caller finds this error waiting for it)
     return RAYEN_E_LAUNCH;
+  }
   const unsigned grid = (unsigned)((a.B + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;

@@ -553,6 +553,7 @@ class Dc3Pack:
     def __init__(self, arrays, device_index):
         a = arrays
         self.n, self.k = int(a["n"]), int(a["k"])
+        self.inequalities = int(a["A1e"].shape[0]) + int(a["Pe"].shape[0])
         self.device_index = int(device_index)
         handle = ctypes.c_void_p()
         ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
@@ -605,6 +606,10 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
     _dc3_check(q, pack)
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
+    if pack.inequalities == 0:
+        # the reference never meets its stop rule on a set without inequalities (dc3.reference_forward: nothing is
+        # stacked) and runs to the limit; the kernels' violations are all 0 there, and 0 < 0 is false
+        eps = 0.0
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     steps = torch.empty((1,), dtype=torch.int32, device=q.device)
     with _on_device(q.device):
