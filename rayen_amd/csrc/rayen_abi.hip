@@ -43,6 +43,19 @@ int check_table(const RayenPackDesc* d) {
 template <typename T> GenericImage<T>& image_of(const RayenPack* p);
 template <> GenericImage<float>& image_of<float>(const RayenPack* p) { return p->g32; }
 template <> GenericImage<double>& image_of<double>(const RayenPack* p) { return p->g64; }
+template <typename T> bool is_mixed(const RayenPack* p) { return sizeof(T) == 4 ? p->mixed32 : p->mixed64; }   // (mixed_forward)
+template <typename T> LmiQuadImage* lmi_quad_of(const RayenPack* p) { return sizeof(T) == 4 ? p->q32 : p->q64; }
+template <typename T> LmiWaveImage* lmi_wave_of(const RayenPack* p) { return sizeof(T) == 4 ? p->w32 : p->w64; }
+
+// what the dispatch of the LMI kernel families needs to know per precision
+template <typename T> struct LmiTraits {
+  static constexpr bool f64 = sizeof(T) == 8;                       // (the flag lmi_block_preferred takes)
+  // a pack the quad kernel holds gets a wave image as well only beyond this r (the block / wave kernels are faster there)
+  static constexpr int quad_build_cutoff = f64 ? 20 : 28;
+  // four lanes per sample pay off while one lane per sample cannot fill the chip (B/64 waves on 1024 SIMDs x 2); beyond
+  // that the lane-per-sample kernel has the higher throughput in fp32
+  static constexpr int64_t quad_batch_cap = f64 ? INT64_MAX : 65536;
+};
 
 // which kernel family served this thread's most recent forward call (rayen_last_forward_kernel)
 thread_local int g_last_forward = RAYEN_KERNEL_NONE;
@@ -114,6 +127,20 @@ int lmi_dim(const RayenPack* p) {
   return r;
 }
 
+// the images of the LMI kernel families, in one precision
+template <typename T>
+int build_lmi_images(RayenPack* p) {
+  LmiQuadImage*& q = sizeof(T) == 4 ? p->q32 : p->q64;
+  LmiWaveImage*& w = sizeof(T) == 4 ? p->w32 : p->w64;
+  int rc = RAYEN_OK;
+  if ((rc = build_one(p, lmi_quad_eligible<T>(p), &q, lmi_quad_build<T>))) return rc;
+  // (the wave-per-sample LMI kernels take what neither the quad kernel nor the lane kernels hold: matrices beyond ~30 x 30)
+  const bool beyond_quad = q == nullptr || lmi_dim(p) > LmiTraits<T>::quad_build_cutoff;
+  if ((rc = build_one(p, (lmi_wave_eligible<T>(p) || lmi_block_eligible<T>(p) || is_mixed<T>(p)) && beyond_quad, &w, lmi_wave_build<T>)))
+    return rc;
+  return w != nullptr ? lmi_block_prepare<T>(w) : RAYEN_OK;
+}
+
 int build_images(RayenPack* p, int prepare) {
   // (no precision bit = both precisions: RAYEN_PREPARE_FWD_ONLY alone means "forward only, fp32 and fp64")
   const bool f32 = (prepare & (RAYEN_PREPARE_F32 | RAYEN_PREPARE_F64)) == 0 || (prepare & RAYEN_PREPARE_F32);
@@ -141,7 +168,7 @@ int build_images(RayenPack* p, int prepare) {
   }
   if (f32) {
     p->prepared |= RAYEN_PREPARE_F32;
-    p->mixed32 = lmi_block_eligible_mixed_f32(p) && !generic_holds_lmis<float>(p);
+    p->mixed32 = lmi_block_eligible_mixed<float>(p) && !generic_holds_lmis<float>(p);
     p->g32.skip_lmi = p->mixed32;
     if ((rc = build_generic<float>(p))) return rc;
     if ((rc = build_one(p, mfma_eligible(p), &p->m32, mfma_build))) return rc;
@@ -156,10 +183,7 @@ int build_images(RayenPack* p, int prepare) {
       // (the instances behind the fused mapper walk an image without shared tiles, rayen_mfma_pair.hip)
       if (p->pr32 != nullptr && mfma_pair_has_halves(p->pr32) && (rc = build_one(p, true, &p->pr32m, mfma_pair_build_dense))) return rc;
     }
-    if ((rc = build_one(p, lmi_quad_eligible_f32(p), &p->q32, lmi_quad_build_f32))) return rc;
-    // (the wave-per-sample LMI kernels take what neither the quad kernel nor the lane kernels hold: matrices beyond ~30 x 30)
-    if ((rc = build_one(p, (lmi_wave_eligible_f32(p) || lmi_block_eligible_f32(p) || p->mixed32) && (p->q32 == nullptr || lmi_dim(p) > 28), &p->w32, lmi_wave_build_f32))) return rc;
-    if (p->w32 != nullptr && (rc = lmi_block_prepare_f32(p->w32))) return rc;
+    if ((rc = build_lmi_images<float>(p))) return rc;
     if (bwd) {
       if ((rc = build_one(p, mfma_bwd_eligible(p), &p->mb32, mfma_bwd_build))) return rc;
       // (f16 pairs in the backward follow the forward's switch: fp32_mode 0 measured, 3 unmeasured, 1 / 2 / 4 never)
@@ -176,13 +200,11 @@ int build_images(RayenPack* p, int prepare) {
   if (!restore.keep.empty()) { p->W.swap(restore.keep); restore.keep.clear(); }     // (the exact rows again)
   if (f64) {
     p->prepared |= RAYEN_PREPARE_F64;
-    p->mixed64 = lmi_block_eligible_mixed_f64(p) && !generic_holds_lmis<double>(p);
+    p->mixed64 = lmi_block_eligible_mixed<double>(p) && !generic_holds_lmis<double>(p);
     p->g64.skip_lmi = p->mixed64;
     if ((rc = build_generic<double>(p))) return rc;
     if ((rc = build_one(p, mfma64_eligible(p), &p->m64, mfma64_build))) return rc;
-    if ((rc = build_one(p, lmi_quad_eligible_f64(p), &p->q64, lmi_quad_build_f64))) return rc;
-    if ((rc = build_one(p, (lmi_wave_eligible_f64(p) || lmi_block_eligible_f64(p) || p->mixed64) && (p->q64 == nullptr || lmi_dim(p) > 20), &p->w64, lmi_wave_build_f64))) return rc;
-    if (p->w64 != nullptr && (rc = lmi_block_prepare_f64(p->w64))) return rc;
+    if ((rc = build_lmi_images<double>(p))) return rc;
     if (bwd) {
       if ((rc = build_one(p, mfma64_bwd_eligible(p), &p->mb64, mfma64_bwd_build))) return rc;
       if (p->mb64 == nullptr && (rc = build_one(p, mfma64_bwdg_eligible(p), &p->mbg64, mfma64_bwdg_build))) return rc;
@@ -199,8 +221,6 @@ int build_images(RayenPack* p, int prepare) {
 // the LMI (and the linear rows once more), takes the larger of the two and writes y.  The backward is the lane kernel's for
 // every sample (a sample whose active row is the LMI gets s N'g from it) followed by the workgroup kernel on the samples
 // the LMI clipped.
-template <typename T> bool is_mixed(const RayenPack* p) { return sizeof(T) == 4 ? p->mixed32 : p->mixed64; }
-
 template <typename T>
 int mixed_forward(const RayenPack* p, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy, T* kappa, int32_t* active,
                   int32_t* nan_flag, int old_mode, hipStream_t stream) {
@@ -213,10 +233,7 @@ int mixed_forward(const RayenPack* p, const T* v, int64_t B, int64_t ldv, T* y, 
                                     stream, ldk);
   if (rc) return rc;
   g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
-  if constexpr (sizeof(T) == 4)
-    return lmi_block_forward_f32(p, p->w32, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, between, ldk, old_mode);
-  else
-    return lmi_block_forward_f64(p, p->w64, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, between, ldk, old_mode);
+  return lmi_block_forward<T>(p, lmi_wave_of<T>(p), v, B, ldv, y, ldy, kappa, active, nan_flag, stream, between, ldk, old_mode);
 }
 
 template <typename T>
@@ -247,12 +264,12 @@ int project_bwd(const RayenPack* p, const T* v, int64_t B, int64_t ldv, const T*
   if (B > 0 && (!v || !kappa || !active || !grad_y || !grad_v)) return RAYEN_E_BAD_ARG;
   int rc = check_ready<T>(p, true);
   if (rc) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const LmiQuadImage* q = lmi_quad_of<T>(p);
+  const LmiWaveImage* w = lmi_wave_of<T>(p);
+  if (!force_generic && !old_mode && q != nullptr && lmi_quad_bwd_serves<T>(p, q))
+    return lmi_quad_backward<T>(p, q, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, st);
   if constexpr (sizeof(T) == 4) {
-    if (!force_generic && !old_mode) {
-      if (p->q32 != nullptr && lmi_quad_bwd_serves_f32(p, p->q32))
-        return lmi_quad_backward_f32(p, p->q32, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                     static_cast<hipStream_t>(stream));
-    }
     if (!force_generic) {
       if (p->mbd32 != nullptr && p->mbd32_state == 1 && !old_mode && dense_pairs_backward_enabled() &&
           mfma_bwdd_serves(p, p->mbd32, v, B, ldv, grad_y, ldg, grad_v, ldgv))
@@ -270,11 +287,6 @@ int project_bwd(const RayenPack* p, const T* v, int64_t B, int64_t ldv, const T*
     }
   }
   if constexpr (sizeof(T) == 8) {
-    if (!force_generic && !old_mode) {
-      if (p->q64 != nullptr && lmi_quad_bwd_serves_f64(p, p->q64))
-        return lmi_quad_backward_f64(p, p->q64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                     static_cast<hipStream_t>(stream));
-    }
     if (!force_generic) {
       if (p->mb64 != nullptr)
         return mfma64_backward(p, p->mb64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, old_mode, workspace,
@@ -284,47 +296,43 @@ int project_bwd(const RayenPack* p, const T* v, int64_t B, int64_t ldv, const T*
                                     static_cast<hipStream_t>(stream));
     }
   }
-  const int rcg = generic_backward<T>(p, image_of<T>(p), v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                      old_mode, static_cast<hipStream_t>(stream));
-  if (rcg == RAYEN_OK && is_mixed<T>(p)) {        // (the lane kernel has left out the LMI's term: see mixed_forward)
-    if constexpr (sizeof(T) == 4)
-      return lmi_block_backward_f32(p, p->w32, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                    static_cast<hipStream_t>(stream), 1, old_mode);
-    else
-      return lmi_block_backward_f64(p, p->w64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                    static_cast<hipStream_t>(stream), 1, old_mode);
+  const int rcg = generic_backward<T>(p, image_of<T>(p), v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, old_mode, st);
+  if (rcg == RAYEN_OK && is_mixed<T>(p))          // (the lane kernel has left out the LMI's term: see mixed_forward)
+    return lmi_block_backward<T>(p, w, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, st, 1, old_mode);
+  if (rcg != RAYEN_E_UNSUPPORTED || w == nullptr) return rcg;
+  // (nothing was launched)
+  if (old_mode)      // (the RAYEN_old head: the workgroup-per-sample kernels have it, the wave kernels do not)
+    return lmi_block_bwd_serves<T>(w) ? lmi_block_backward<T>(p, w, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, st, 0, 1)
+                                      : rcg;
+  if (lmi_block_preferred(lmi_block_bwd_serves<T>(w), lmi_wave_serves<T>(w), lmi_dim(p), LmiTraits<T>::f64))
+    return lmi_block_backward<T>(p, w, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, st);
+  return lmi_wave_backward<T>(p, w, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, st);
+}
+
+// The forward ladder below the matrix-core kernels, the same in both precisions: the quad kernel where the pack has its
+// image, else the lane kernels, else (they launched nothing) the workgroup- or wave-per-sample kernel.
+template <typename T>
+int project_lanes_or_lmi(const RayenPack* p, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy, T* kappa,
+                         int32_t* active, int32_t* nan_flag, hipStream_t stream, int old_mode) {
+  if (y != nullptr && !old_mode && B <= LmiTraits<T>::quad_batch_cap && lmi_quad_of<T>(p) != nullptr) {
+    g_last_forward = RAYEN_KERNEL_LMI_QUAD;
+    return lmi_quad_forward<T>(p, lmi_quad_of<T>(p), v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
   }
-  if (rcg == RAYEN_E_UNSUPPORTED && old_mode) {    // (the RAYEN_old head: the workgroup-per-sample kernels have it, the wave kernels do not)
-    if constexpr (sizeof(T) == 4) {
-      if (p->w32 != nullptr && lmi_block_bwd_serves_f32(p->w32))
-        return lmi_block_backward_f32(p, p->w32, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                      static_cast<hipStream_t>(stream), 0, 1);
-    } else {
-      if (p->w64 != nullptr && lmi_block_bwd_serves_f64(p->w64))
-        return lmi_block_backward_f64(p, p->w64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                      static_cast<hipStream_t>(stream), 0, 1);
-    }
+  g_last_forward = RAYEN_KERNEL_LANE;
+  const int rcg = project_generic<T>(p, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, old_mode);
+  const LmiWaveImage* w = lmi_wave_of<T>(p);
+  if (rcg != RAYEN_E_UNSUPPORTED || w == nullptr || y == nullptr) return rcg;
+  if (old_mode) {        // (the RAYEN_old head: only the workgroup-per-sample kernel has it)
+    if (is_mixed<T>(p) || !lmi_block_serves<T>(w)) return rcg;
+    g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
+    return lmi_block_forward<T>(p, w, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, nullptr, 1, 1);
   }
-  if (rcg == RAYEN_E_UNSUPPORTED && !old_mode) {   // (nothing was launched)
-    if constexpr (sizeof(T) == 4) {
-      if (p->w32 != nullptr) {
-        if (lmi_block_preferred(lmi_block_bwd_serves_f32(p->w32), lmi_wave_serves_f32(p->w32), lmi_dim(p), false))
-          return lmi_block_backward_f32(p, p->w32, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                        static_cast<hipStream_t>(stream));
-        return lmi_wave_backward_f32(p, p->w32, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                     static_cast<hipStream_t>(stream));
-      }
-    } else {
-      if (p->w64 != nullptr) {
-        if (lmi_block_preferred(lmi_block_bwd_serves_f64(p->w64), lmi_wave_serves_f64(p->w64), lmi_dim(p), true))
-          return lmi_block_backward_f64(p, p->w64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                        static_cast<hipStream_t>(stream));
-        return lmi_wave_backward_f64(p, p->w64, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv,
-                                     static_cast<hipStream_t>(stream));
-      }
-    }
+  if (lmi_block_preferred(lmi_block_serves<T>(w), lmi_wave_serves<T>(w), lmi_dim(p), LmiTraits<T>::f64)) {
+    g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
+    return lmi_block_forward<T>(p, w, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
   }
-  return rcg;
+  g_last_forward = RAYEN_KERNEL_LMI_WAVE;
+  return lmi_wave_forward<T>(p, w, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
 }
 
 // [linear rows] + ONE LMI on the workgroup-per-sample kernels, with nothing else in the set: such a pack also takes the
@@ -333,7 +341,7 @@ bool lmi_products_pack(const RayenPack* p) {
   if (p->mixed32 || p->mixed64 || p->q32 != nullptr || p->q64 != nullptr) return false;   // (the four-lane kernel's sizes stay with it)
   for (const RayenSegment& g : p->segs)
     if (g.type != RAYEN_SEG_LIN && g.type != RAYEN_SEG_LMI) return false;
-  return (p->w32 != nullptr && lmi_block_products_serves_f32(p->w32)) || (p->w64 != nullptr && lmi_block_products_serves_f64(p->w64));
+  return lmi_block_products_serves<float>(p->w32) || lmi_block_products_serves<double>(p->w64);   // (false for a null image)
 }
 
 template <typename T>
@@ -348,14 +356,84 @@ int project_from_products(const RayenPack* p, const T* Tm, int64_t ldt, const T*
   if (p->wide == nullptr && lmi_products_pack(p)) {      // [linear rows] + one LMI: the workgroup-per-sample kernel reads S(v) from T
     if (y == nullptr) return RAYEN_E_UNSUPPORTED;
     g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
-    if constexpr (sizeof(T) == 4)
-      return lmi_block_forward_products_f32(p, p->w32, Tm, ldt, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    else
-      return lmi_block_forward_products_f64(p, p->w64, Tm, ldt, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
+    return lmi_block_forward_products<T>(p, lmi_wave_of<T>(p), Tm, ldt, v, B, ldv, y, ldy, kappa, active, nan_flag,
+                                         static_cast<hipStream_t>(stream));
   }
   return wide_epilogue<T>(p, p->wide, Tm, ldt, v, B, ldv, y, ldy, kappa, active, nan_flag,
                           static_cast<hipStream_t>(stream));
 }
+
+template <typename T>
+int project_bwd_coefficients(const RayenPack* p, const T* Tm, int64_t ldt, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                             const int32_t* active, const T* grad_y, int64_t ldg, T* C, int64_t ldc, T* gs, void* stream) {
+  if (p == nullptr || B < 0 || ldv < p->n || ldg < p->k || ldt < (int64_t)p->n_rows + (p->out_identity ? 0 : p->k) ||
+      ldc < (int64_t)p->n_rows + (p->out_identity ? 0 : p->k) || (p->out_identity && gs == nullptr && B > 0))
+    return RAYEN_E_BAD_ARG;
+  if (B > 0 && (!Tm || !v || !kappa || !active || !grad_y || !C)) return RAYEN_E_BAD_ARG;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;
+  if (dev != p->device) return RAYEN_E_DEVICE_MISMATCH;
+  if (p->wide == nullptr && lmi_products_pack(p))
+    return lmi_block_bwd_coefficients<T>(p, lmi_wave_of<T>(p), Tm, ldt, v, B, ldv, kappa, active, grad_y, ldg, C, ldc, gs,
+                                         static_cast<hipStream_t>(stream));
+  return wide_bwd_coefficients<T>(p, p->wide, Tm, ldt, v, B, ldv, kappa, active, grad_y, ldg, C, ldc, gs,
+                                  static_cast<hipStream_t>(stream));
+}
+
+// ---- what the two creation-time measurements (fp32_selfcheck, bwd32_selfcheck) share ----
+
+// their random numbers: a 32-bit LCG, uniform in (-1, 1)
+struct ProbeLcg {
+  uint32_t state;
+  float operator()() {
+    state = state * 1664525u + 1013904223u;
+    return (float)(state >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  }
+};
+
+// their rule: a split-operand kernel may serve the pack if its worst row error against fp64 is below 4e-6 of the row's size or
+// within 1.5 x the exact-fp32 kernel's own
+bool accepted(double worst, double exact) { return worst <= 4e-6 || (std::isfinite(exact) && worst <= 1.5 * exact); }
+
+// their yardstick, the fp64 lane image, which a pack prepared for fp32 only does not have: built for the measurement and
+// released after it (the pack keeps it, and counts its bytes, if fp64 was asked for and it is merely not built yet)
+struct Fp64Yardstick {
+  RayenPack* p;
+  bool own_g64 = false;
+  int rc = RAYEN_OK;
+  explicit Fp64Yardstick(RayenPack* pack) : p(pack) {
+    if (p->g64.built) return;
+    rc = generic_build<double>(p, &p->g64);
+    if (rc != RAYEN_OK) { generic_free<double>(&p->g64); return; }
+    own_g64 = !(p->prepared & RAYEN_PREPARE_F64);
+    if (!own_g64) p->device_bytes += p->g64.bytes;
+  }
+  ~Fp64Yardstick() { if (own_g64) generic_free<double>(&p->g64); }
+  Fp64Yardstick(const Fp64Yardstick&) = delete;
+  Fp64Yardstick& operator=(const Fp64Yardstick&) = delete;
+};
+
+// their private non-blocking stream and device buffers, all released by the destructor.  A failure is sticky: once the
+// stream or an allocation has failed, alloc() returns null without asking the runtime again.
+struct CheckScratch {
+  hipStream_t stream = nullptr;
+  bool ok = false;
+  std::vector<void*> owned;
+  CheckScratch() { ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
+  ~CheckScratch() {
+    for (void* ptr : owned) (void)hipFree(ptr);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  CheckScratch(const CheckScratch&) = delete;
+  CheckScratch& operator=(const CheckScratch&) = delete;
+  template <typename T>
+  T* alloc(size_t count) {
+    void* ptr = nullptr;
+    ok = ok && hipMalloc(&ptr, count * sizeof(T)) == hipSuccess;
+    if (ptr != nullptr) owned.push_back(ptr);
+    return static_cast<T*>(ptr);
+  }
+};
 
 }  // namespace
 
@@ -414,17 +492,13 @@ static int fp32_selfcheck(RayenPack* p) {
   }
   const int n = p->n, k = p->k;
   std::vector<float> hv;
-  uint32_t state = 0x9E3779B9u;
-  auto uniform = [&state]() {
-    state = state * 1664525u + 1013904223u;
-    return (float)(state >> 8) * (1.0f / 8388608.0f) - 1.0f;  // (-1, 1)
-  };
+  ProbeLcg uniform{0x9E3779B9u};
   for (int b = 0; b < 512; ++b) for (int j = 0; j < n; ++j) hv.push_back(1.5f * uniform());
   for (int b = 0; b < 256; ++b) for (int j = 0; j < n; ++j) hv.push_back(96.0f * uniform());
   // (the f16-pair kernel scales every row by its own power of two: a row with components spread over many binades
   // is its worst case)
   for (int b = 0; b < 128; ++b)
-    for (int j = 0; j < n; ++j) hv.push_back(std::ldexp(uniform(), -(int)((state >> 3) % 20u)));
+    for (int j = 0; j < n; ++j) hv.push_back(std::ldexp(uniform(), -(int)((uniform.state >> 3) % 20u)));
   const int rows = p->n_rows, take = rows < 384 ? rows : 384;
   for (int t = 0; t < take; ++t) {
     const double* w = &p->W[(size_t)((int64_t)t * rows / take) * n];
@@ -508,44 +582,33 @@ static int fp32_selfcheck(RayenPack* p) {
   std::vector<double> hvd(hv.begin(), hv.end());
   std::vector<float> yf(3 * ny);      // triple | exact | pair
   std::vector<double> yt(ny);
-  // the yardstick needs the fp64 lane image even when the caller asked for fp32 only
-  bool own_g64 = false;
   int rc = RAYEN_OK;
-  if (!p->g64.built) {
-    rc = generic_build<double>(p, &p->g64);
-    if (rc != RAYEN_OK) { generic_free<double>(&p->g64); return rc; }
-    own_g64 = !(p->prepared & RAYEN_PREPARE_F64);
-    if (!own_g64) p->device_bytes += p->g64.bytes;
+  bool ok = false;
+  {
+    Fp64Yardstick yardstick(p);
+    if (yardstick.rc != RAYEN_OK) return yardstick.rc;
+    CheckScratch scratch;
+    float* dv = scratch.alloc<float>(hv.size());
+    double* dvd = scratch.alloc<double>(hvd.size());
+    float* dyf = scratch.alloc<float>(yf.size());
+    double* dyt = scratch.alloc<double>(yt.size());
+    const hipStream_t st = scratch.stream;
+    ok = scratch.ok && hipMemsetAsync(dyf, 0, yf.size() * sizeof(float), st) == hipSuccess &&
+         hipMemcpyAsync(dv, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dvd, hvd.data(), hvd.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+      if (p->sp32 != nullptr) rc = mfma_split_forward(p, p->sp32, dv, B0, n, dyf, k, nullptr, nullptr, nullptr, st);
+      if (rc == RAYEN_OK) rc = mfma_forward(p, p->m32, dv, B0, n, dyf + ny, k, nullptr, nullptr, nullptr, 0, st);
+      if (rc == RAYEN_OK && p->pr32 != nullptr)
+        rc = mfma_pair_forward(p, p->pr32, dv, B0, n, dyf + 2 * ny, k, nullptr, nullptr, nullptr, st);
+      if (rc == RAYEN_OK)
+        rc = generic_forward<double>(p, p->g64, dvd, B0, n, dyt, k, nullptr, nullptr, nullptr, 0, st);
+      ok = rc == RAYEN_OK &&
+           hipMemcpyAsync(yf.data(), dyf, yf.size() * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipMemcpyAsync(yt.data(), dyt, yt.size() * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+    }
   }
-  hipStream_t st = nullptr;
-  float *dv = nullptr, *dyf = nullptr;
-  double *dvd = nullptr, *dyt = nullptr;
-  bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&dv, hv.size() * sizeof(float)) == hipSuccess &&
-            hipMalloc(&dvd, hvd.size() * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dyf, yf.size() * sizeof(float)) == hipSuccess &&
-            hipMalloc(&dyt, yt.size() * sizeof(double)) == hipSuccess &&
-            hipMemsetAsync(dyf, 0, yf.size() * sizeof(float), st) == hipSuccess &&
-            hipMemcpyAsync(dv, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(dvd, hvd.data(), hvd.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    if (p->sp32 != nullptr) rc = mfma_split_forward(p, p->sp32, dv, B0, n, dyf, k, nullptr, nullptr, nullptr, st);
-    if (rc == RAYEN_OK) rc = mfma_forward(p, p->m32, dv, B0, n, dyf + ny, k, nullptr, nullptr, nullptr, 0, st);
-    if (rc == RAYEN_OK && p->pr32 != nullptr)
-      rc = mfma_pair_forward(p, p->pr32, dv, B0, n, dyf + 2 * ny, k, nullptr, nullptr, nullptr, st);
-    if (rc == RAYEN_OK)
-      rc = generic_forward<double>(p, p->g64, dvd, B0, n, dyt, k, nullptr, nullptr, nullptr, 0, st);
-    ok = rc == RAYEN_OK &&
-         hipMemcpyAsync(yf.data(), dyf, yf.size() * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipMemcpyAsync(yt.data(), dyt, yt.size() * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;
-  }
-  if (dv) (void)hipFree(dv);
-  if (dvd) (void)hipFree(dvd);
-  if (dyf) (void)hipFree(dyf);
-  if (dyt) (void)hipFree(dyt);
-  if (st) (void)hipStreamDestroy(st);
-  if (own_g64) generic_free<double>(&p->g64);
   if (!ok) return rc != RAYEN_OK ? rc : RAYEN_E_ALLOC;
   double worst[3] = {0.0, 0.0, 0.0};
   bool broken[3] = {false, false, false};   // a NaN / inf where the yardstick is finite: sticky, the family is out
@@ -569,9 +632,8 @@ static int fp32_selfcheck(RayenPack* p) {
   for (int f = 0; f < 3; ++f)
     if (broken[f]) worst[f] = std::numeric_limits<double>::infinity();
   p->check_exact = worst[1];
-  auto accept = [&](double w) { return (w <= 4e-6 || (std::isfinite(worst[1]) && w <= 1.5 * worst[1])) ? 1 : 2; };
-  if (p->sp32 != nullptr) { p->check_split = worst[0]; p->sp32_state = accept(worst[0]); }
-  if (p->pr32 != nullptr) { p->check_pair = worst[2]; p->pr32_state = accept(worst[2]); }
+  if (p->sp32 != nullptr) { p->check_split = worst[0]; p->sp32_state = accepted(worst[0], worst[1]) ? 1 : 2; }
+  if (p->pr32 != nullptr) { p->check_pair = worst[2]; p->pr32_state = accepted(worst[2], worst[1]) ? 1 : 2; }
   return RAYEN_OK;
 }
 
@@ -588,73 +650,64 @@ static int bwd32_selfcheck(RayenPack* p) {
   if (dense && p->fp32_mode == 3) { p->mbd32_state = 1; return RAYEN_OK; }
   if (!dense && (p->fp32_mode == 3 || p->mbg32 == nullptr)) { p->mbp32_state = 1; return RAYEN_OK; }
   const int n = p->n, k = p->k;
-  uint32_t state = 0x2545F491u;
-  auto uniform = [&state]() {
-    state = state * 1664525u + 1013904223u;
-    return (float)(state >> 8) * (1.0f / 8388608.0f) - 1.0f;
-  };
+  ProbeLcg uniform{0x2545F491u};
   std::vector<float> hv, hg;
   for (int b = 0; b < 384; ++b) for (int j = 0; j < n; ++j) hv.push_back(1.5f * uniform());
   for (int b = 0; b < 384; ++b) for (int j = 0; j < n; ++j) hv.push_back(12.0f * uniform());
   for (int b = 0; b < 256; ++b) for (int j = 0; j < n; ++j) hv.push_back(96.0f * uniform());
   const int64_t B0 = (int64_t)(hv.size() / (size_t)n);
   for (int64_t b = 0; b < B0; ++b)
-    for (int j = 0; j < k; ++j) hg.push_back(b % 5 == 4 ? std::ldexp(uniform(), -(int)((state >> 3) % 16u)) : uniform());
+    for (int j = 0; j < k; ++j) hg.push_back(b % 5 == 4 ? std::ldexp(uniform(), -(int)((uniform.state >> 3) % 16u)) : uniform());
   std::vector<double> hvd(hv.begin(), hv.end()), hgd(hg.begin(), hg.end());
-  bool own_g64 = false;
-  int rc = RAYEN_OK;
-  if (!p->g64.built) {
-    rc = generic_build<double>(p, &p->g64);
-    if (rc != RAYEN_OK) { generic_free<double>(&p->g64); return rc; }
-    own_g64 = !(p->prepared & RAYEN_PREPARE_F64);
-    if (!own_g64) p->device_bytes += p->g64.bytes;
-  }
   const size_t nv = (size_t)B0 * n, ng = (size_t)B0 * k;
   std::vector<double> kap64((size_t)B0), gt(nv);
   std::vector<float> kap32((size_t)B0), gf(2 * nv);
-  hipStream_t st = nullptr;
-  float *dv = nullptr, *dg = nullptr, *dk = nullptr, *dgf = nullptr;
-  double *dvd = nullptr, *dgd = nullptr, *dkd = nullptr, *dyd = nullptr, *dgt = nullptr;
-  int32_t* dact = nullptr;
-  bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc(&dv, nv * sizeof(float)) == hipSuccess && hipMalloc(&dg, ng * sizeof(float)) == hipSuccess &&
-            hipMalloc(&dk, (size_t)B0 * sizeof(float)) == hipSuccess && hipMalloc(&dgf, 2 * nv * sizeof(float)) == hipSuccess &&
-            hipMalloc(&dvd, nv * sizeof(double)) == hipSuccess && hipMalloc(&dgd, ng * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dkd, (size_t)B0 * sizeof(double)) == hipSuccess && hipMalloc(&dyd, ng * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dgt, nv * sizeof(double)) == hipSuccess && hipMalloc(&dact, (size_t)B0 * 2 * sizeof(int32_t)) == hipSuccess &&
-            hipMemsetAsync(dgf, 0, 2 * nv * sizeof(float), st) == hipSuccess &&
-            hipMemcpyAsync(dv, hv.data(), nv * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(dg, hg.data(), ng * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(dvd, hvd.data(), nv * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(dgd, hgd.data(), ng * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    rc = generic_forward<double>(p, p->g64, dvd, B0, n, dyd, k, dkd, dact, nullptr, 0, st);
-    if (rc == RAYEN_OK)
-      rc = generic_backward<double>(p, p->g64, dvd, B0, n, dkd, dact, dgd, k, dgt, n, 0, st);
-    ok = rc == RAYEN_OK &&
-         hipMemcpyAsync(kap64.data(), dkd, (size_t)B0 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;
+  int rc = RAYEN_OK;
+  bool ok = false;
+  {
+    Fp64Yardstick yardstick(p);
+    if (yardstick.rc != RAYEN_OK) return yardstick.rc;
+    CheckScratch scratch;
+    float* dv = scratch.alloc<float>(nv);
+    float* dg = scratch.alloc<float>(ng);
+    float* dk = scratch.alloc<float>((size_t)B0);
+    float* dgf = scratch.alloc<float>(2 * nv);
+    double* dvd = scratch.alloc<double>(nv);
+    double* dgd = scratch.alloc<double>(ng);
+    double* dkd = scratch.alloc<double>((size_t)B0);
+    double* dyd = scratch.alloc<double>(ng);
+    double* dgt = scratch.alloc<double>(nv);
+    int32_t* dact = scratch.alloc<int32_t>((size_t)B0 * 2);
+    const hipStream_t st = scratch.stream;
+    ok = scratch.ok && hipMemsetAsync(dgf, 0, 2 * nv * sizeof(float), st) == hipSuccess &&
+         hipMemcpyAsync(dv, hv.data(), nv * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dg, hg.data(), ng * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dvd, hvd.data(), nv * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dgd, hgd.data(), ng * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok) {
-      for (int64_t b = 0; b < B0; ++b) kap32[(size_t)b] = (float)kap64[(size_t)b];
-      ok = hipMemcpyAsync(dk, kap32.data(), (size_t)B0 * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (ok) {
-      rc = dense ? mfma_bwdd_backward(p, p->mbd32, dv, B0, n, dk, dact, dg, k, dgf, n, st)
-                 : mfma_bwdp_backward(p, p->mbp32, dv, B0, n, dk, dact, dg, k, dgf, n, st);
+      rc = generic_forward<double>(p, p->g64, dvd, B0, n, dyd, k, dkd, dact, nullptr, 0, st);
       if (rc == RAYEN_OK)
-        rc = dense ? mfma_backward(p, p->mb32, dv, B0, n, dk, dact, dg, k, dgf + nv, n, 0, nullptr, 0, st)
-                   : mfma_bwdg_backward(p, p->mbg32, dv, B0, n, dk, dact, dg, k, dgf + nv, n, 0, nullptr, 0, st);
+        rc = generic_backward<double>(p, p->g64, dvd, B0, n, dkd, dact, dgd, k, dgt, n, 0, st);
       ok = rc == RAYEN_OK &&
-           hipMemcpyAsync(gf.data(), dgf, 2 * nv * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
-           hipMemcpyAsync(gt.data(), dgt, nv * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipMemcpyAsync(kap64.data(), dkd, (size_t)B0 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
            hipStreamSynchronize(st) == hipSuccess;
+      if (ok) {
+        for (int64_t b = 0; b < B0; ++b) kap32[(size_t)b] = (float)kap64[(size_t)b];
+        ok = hipMemcpyAsync(dk, kap32.data(), (size_t)B0 * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
+      }
+      if (ok) {
+        rc = dense ? mfma_bwdd_backward(p, p->mbd32, dv, B0, n, dk, dact, dg, k, dgf, n, st)
+                   : mfma_bwdp_backward(p, p->mbp32, dv, B0, n, dk, dact, dg, k, dgf, n, st);
+        if (rc == RAYEN_OK)
+          rc = dense ? mfma_backward(p, p->mb32, dv, B0, n, dk, dact, dg, k, dgf + nv, n, 0, nullptr, 0, st)
+                     : mfma_bwdg_backward(p, p->mbg32, dv, B0, n, dk, dact, dg, k, dgf + nv, n, 0, nullptr, 0, st);
+        ok = rc == RAYEN_OK &&
+             hipMemcpyAsync(gf.data(), dgf, 2 * nv * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(gt.data(), dgt, nv * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+      }
     }
   }
-  for (void* ptr : {(void*)dv, (void*)dg, (void*)dk, (void*)dgf, (void*)dvd, (void*)dgd, (void*)dkd, (void*)dyd,
-                    (void*)dgt, (void*)dact})
-    if (ptr) (void)hipFree(ptr);
-  if (st) (void)hipStreamDestroy(st);
-  if (own_g64) generic_free<double>(&p->g64);
   if (!ok) return rc != RAYEN_OK ? rc : RAYEN_E_ALLOC;
   double worst[2] = {0.0, 0.0};
   bool broken[2] = {false, false};
@@ -677,7 +730,7 @@ static int bwd32_selfcheck(RayenPack* p) {
     if (broken[f]) worst[f] = std::numeric_limits<double>::infinity();
   p->check_bwd_pair = worst[0];
   p->check_bwd_exact = worst[1];
-  (dense ? p->mbd32_state : p->mbp32_state) = (worst[0] <= 4e-6 || (std::isfinite(worst[1]) && worst[0] <= 1.5 * worst[1])) ? 1 : 2;
+  (dense ? p->mbd32_state : p->mbp32_state) = accepted(worst[0], worst[1]) ? 1 : 2;
   return RAYEN_OK;
 }
 
@@ -779,12 +832,12 @@ int rayen_pack_info(const RayenPack* p, RayenPackInfo* info) {
   info->fp32_check_exact = p->check_exact;
   info->fp32_check_pair = p->check_pair;
   info->bwd_f32 = !(p->prepared & 4) ? 0
-                  : (p->q32 != nullptr && lmi_quad_bwd_serves_f32(p, p->q32)) ? 4
+                  : (p->q32 != nullptr && lmi_quad_bwd_serves<float>(p, p->q32)) ? 4
                   : (p->mbd32 != nullptr && p->mbd32_state == 1) ? 7
                   : p->mb32 != nullptr ? 1
                   : (p->mbp32 != nullptr && p->mbp32_state == 1) ? 3
                   : p->mbg32 != nullptr ? 2
-                  : (p->w32 != nullptr && (lmi_wave_serves_f32(p->w32) || lmi_block_bwd_serves_f32(p->w32)) &&
+                  : (p->w32 != nullptr && (lmi_wave_serves<float>(p->w32) || lmi_block_bwd_serves<float>(p->w32)) &&
                      !generic_backward_serves<float>(p, image_of<float>(p))) ? 5 : 0;
   info->bwd32_check_pair = p->check_bwd_pair;
   info->bwd32_check_exact = p->check_bwd_exact;
@@ -819,32 +872,17 @@ int rayen_ray_project_from_products_f64(const RayenPack* p, const double* T, int
   return project_from_products<double>(p, T, ldt, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
 }
 
-#define RAYEN_BWD_COEFF(NAME, T)                                                                                      \
-  int NAME(const RayenPack* p, const T* Tm, int64_t ldt, const T* v, int64_t B, int64_t ldv, const T* kappa,             \
-           const int32_t* active, const T* grad_y, int64_t ldg, T* C, int64_t ldc, T* gs, void* stream) {                \
-    if (p == nullptr || B < 0 || ldv < p->n || ldg < p->k || ldt < (int64_t)p->n_rows + (p->out_identity ? 0 : p->k) ||  \
-        ldc < (int64_t)p->n_rows + (p->out_identity ? 0 : p->k) || (p->out_identity && gs == nullptr && B > 0))          \
-      return RAYEN_E_BAD_ARG;                                                                                            \
-    if (B > 0 && (!Tm || !v || !kappa || !active || !grad_y || !C)) return RAYEN_E_BAD_ARG;                              \
-    int dev = -1;                                                                                                        \
-    if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;                                                      \
-    if (dev != p->device) return RAYEN_E_DEVICE_MISMATCH;                                                                \
-    if (p->wide == nullptr && lmi_products_pack(p)) {                                                                    \
-      if constexpr (sizeof(T) == 4)                                                                                      \
-        return lmi_block_bwd_coefficients_f32(p, p->w32, (const float*)Tm, ldt, (const float*)v, B, ldv,                 \
-                                              (const float*)kappa, active, (const float*)grad_y, ldg, (float*)C, ldc,    \
-                                              (float*)gs, static_cast<hipStream_t>(stream));                             \
-      else                                                                                                               \
-        return lmi_block_bwd_coefficients_f64(p, p->w64, (const double*)Tm, ldt, (const double*)v, B, ldv,               \
-                                              (const double*)kappa, active, (const double*)grad_y, ldg, (double*)C, ldc, \
-                                              (double*)gs, static_cast<hipStream_t>(stream));                            \
-    }                                                                                                                    \
-    return wide_bwd_coefficients<T>(p, p->wide, Tm, ldt, v, B, ldv, kappa, active, grad_y, ldg, C, ldc, gs,              \
-                                    static_cast<hipStream_t>(stream));                                                   \
-  }
-RAYEN_BWD_COEFF(rayen_ray_project_bwd_coefficients_f32, float)
-RAYEN_BWD_COEFF(rayen_ray_project_bwd_coefficients_f64, double)
-#undef RAYEN_BWD_COEFF
+int rayen_ray_project_bwd_coefficients_f32(const RayenPack* p, const float* T, int64_t ldt, const float* v, int64_t B,
+                                           int64_t ldv, const float* kappa, const int32_t* active, const float* grad_y,
+                                           int64_t ldg, float* C, int64_t ldc, float* gs, void* stream) {
+  return project_bwd_coefficients<float>(p, T, ldt, v, B, ldv, kappa, active, grad_y, ldg, C, ldc, gs, stream);
+}
+
+int rayen_ray_project_bwd_coefficients_f64(const RayenPack* p, const double* T, int64_t ldt, const double* v, int64_t B,
+                                           int64_t ldv, const double* kappa, const int32_t* active, const double* grad_y,
+                                           int64_t ldg, double* C, int64_t ldc, double* gs, void* stream) {
+  return project_bwd_coefficients<double>(p, T, ldt, v, B, ldv, kappa, active, grad_y, ldg, C, ldc, gs, stream);
+}
 
 int64_t rayen_products_rows(const RayenPack* p) {
   if (p == nullptr || (p->wide == nullptr && !lmi_products_pack(p))) return 0;
@@ -856,7 +894,7 @@ int rayen_products_served(const RayenPack* p, int f64) {
   if (p == nullptr) return 0;
   if (p->wide != nullptr) return 1;
   if (!lmi_products_pack(p)) return 0;
-  return f64 ? (p->w64 != nullptr && lmi_block_products_serves_f64(p->w64)) : (p->w32 != nullptr && lmi_block_products_serves_f32(p->w32));
+  return f64 ? lmi_block_products_serves<double>(p->w64) : lmi_block_products_serves<float>(p->w32);
 }
 
 static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy,
@@ -879,28 +917,7 @@ static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ld
     return mfma_forward(p, p->m32, v, B, ldv, y, ldy, kappa, active, nan_flag, old_mode,
                         static_cast<hipStream_t>(stream));
   }
-  // four lanes per sample pay off while one lane per sample cannot fill the chip (B/64 waves on
-  // 1024 SIMDs x 2); beyond that the lane-per-sample kernel has the higher throughput in fp32
-  if (y != nullptr && !old_mode && B <= 65536 && p->q32 != nullptr) {
-    g_last_forward = RAYEN_KERNEL_LMI_QUAD;
-    return lmi_quad_forward_f32(p, p->q32, v, B, ldv, y, ldy, kappa, active, nan_flag,
-                                static_cast<hipStream_t>(stream));
-  }
-  g_last_forward = RAYEN_KERNEL_LANE;
-  const int rcg = project_generic<float>(p, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, old_mode);
-  if (rcg == RAYEN_E_UNSUPPORTED && p->w32 != nullptr && y != nullptr && old_mode && !p->mixed32 && lmi_block_serves_f32(p->w32)) {
-    g_last_forward = RAYEN_KERNEL_LMI_BLOCK;       // (the RAYEN_old head: only the workgroup-per-sample kernel has it)
-    return lmi_block_forward_f32(p, p->w32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream), nullptr, 1, 1);
-  }
-  if (rcg == RAYEN_E_UNSUPPORTED && p->w32 != nullptr && y != nullptr && !old_mode) {   // (nothing was launched)
-    if (lmi_block_preferred(lmi_block_serves_f32(p->w32), lmi_wave_serves_f32(p->w32), lmi_dim(p), false)) {
-      g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
-      return lmi_block_forward_f32(p, p->w32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-    }
-    g_last_forward = RAYEN_KERNEL_LMI_WAVE;
-    return lmi_wave_forward_f32(p, p->w32, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-  }
-  return rcg;
+  return project_lanes_or_lmi<float>(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream), old_mode);
 }
 
 int rayen_ray_project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y,
@@ -990,27 +1007,7 @@ static int project_f64(const RayenPack* p, const double* v, int64_t B, int64_t l
     return mfma64_forward(p, p->m64, v, B, ldv, y, ldy, kappa, active, nan_flag, old_mode,
                           static_cast<hipStream_t>(stream));
   }
-  if (y != nullptr && !old_mode && p->q64 != nullptr) {
-    g_last_forward = RAYEN_KERNEL_LMI_QUAD;
-    return lmi_quad_forward_f64(p, p->q64, v, B, ldv, y, ldy, kappa, active, nan_flag,
-                                static_cast<hipStream_t>(stream));
-  }
-  g_last_forward = RAYEN_KERNEL_LANE;
-  const int rcg = project_generic<double>(p, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, old_mode);
-  if (rcg == RAYEN_E_UNSUPPORTED && p->w64 != nullptr && y != nullptr && old_mode && !p->mixed64 && lmi_block_serves_f64(p->w64)) {
-    g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
-    return lmi_block_forward_f64(p, p->w64, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream), nullptr, 1, 1);
-  }
-  if (rcg == RAYEN_E_UNSUPPORTED && p->w64 != nullptr && y != nullptr && !old_mode &&
-      lmi_block_preferred(lmi_block_serves_f64(p->w64), lmi_wave_serves_f64(p->w64), lmi_dim(p), true)) {
-    g_last_forward = RAYEN_KERNEL_LMI_BLOCK;
-    return lmi_block_forward_f64(p, p->w64, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-  }
-  if (rcg == RAYEN_E_UNSUPPORTED && p->w64 != nullptr && y != nullptr && !old_mode) {
-    g_last_forward = RAYEN_KERNEL_LMI_WAVE;
-    return lmi_wave_forward_f64(p, p->w64, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
-  }
-  return rcg;
+  return project_lanes_or_lmi<double>(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream), old_mode);
 }
 
 int rayen_ray_project_f64(const RayenPack* p, const double* v, int64_t B, int64_t ldv, double* y,
@@ -1031,7 +1028,7 @@ int rayen_ray_project_bwd_f32(const RayenPack* p, const float* v, int64_t B, int
 
 int64_t rayen_bwd_workspace_bytes_f32(const RayenPack* p, int64_t B) {
   if (p == nullptr || B <= 0 || check_ready<float>(p, true) != RAYEN_OK) return 0;
-  if (p->q32 != nullptr && lmi_quad_bwd_serves_f32(p, p->q32)) return 0;
+  if (p->q32 != nullptr && lmi_quad_bwd_serves<float>(p, p->q32)) return 0;
   // (the f16-pair backwards stream the batch in order: nothing to sort.  The dense-form one declines rows that are not 16-byte
   // aligned -- the bucketed walk then runs unsorted, same results)
   if (p->mbd32 != nullptr && p->mbd32_state == 1 && dense_pairs_backward_enabled() &&
@@ -1044,7 +1041,7 @@ int64_t rayen_bwd_workspace_bytes_f32(const RayenPack* p, int64_t B) {
 
 int64_t rayen_bwd_workspace_bytes_f64(const RayenPack* p, int64_t B) {
   if (p == nullptr || B <= 0 || check_ready<double>(p, true) != RAYEN_OK) return 0;
-  if (p->q64 != nullptr && lmi_quad_bwd_serves_f64(p, p->q64)) return 0;
+  if (p->q64 != nullptr && lmi_quad_bwd_serves<double>(p, p->q64)) return 0;
   return p->mb64 != nullptr ? mfma64_bwd_workspace_bytes(p, p->mb64, B) : 0;
 }
 

@@ -265,18 +265,21 @@ int mfma_backward(const RayenPack* p, const MfmaBwdImage* img, const float* v, i
                   const float* kappa, const int32_t* active, const float* grad_y, int64_t ldg, float* grad_v,
                   int64_t ldgv, int old_mode, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
-// four-lanes-per-sample LMI kernels (rayen_lmi_quad32.hip / rayen_lmi_quad64.hip)
-bool lmi_quad_eligible_f32(const RayenPack* p);
-bool lmi_quad_eligible_f64(const RayenPack* p);
-int lmi_quad_build_f32(const RayenPack* p, LmiQuadImage** out, int64_t* bytes);
-int lmi_quad_build_f64(const RayenPack* p, LmiQuadImage** out, int64_t* bytes);
+// The LMI kernel families below: one interface per family, templated on the element type.  Each is defined in the
+// family's header and instantiated in its translation units (float in *32.hip, double in *64.hip, both in
+// rayen_lmi_block.hip).
+
+// four lanes per sample (rayen_lmi_quad.h)
+template <typename T> bool lmi_quad_eligible(const RayenPack* p);
+template <typename T> int lmi_quad_build(const RayenPack* p, LmiQuadImage** out, int64_t* bytes);
 void lmi_quad_free(LmiQuadImage* img);
-int lmi_quad_forward_f32(const RayenPack* p, const LmiQuadImage* img, const float* v, int64_t B, int64_t ldv,
-                         float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
-                         hipStream_t stream);
-int lmi_quad_forward_f64(const RayenPack* p, const LmiQuadImage* img, const double* v, int64_t B, int64_t ldv,
-                         double* y, int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag,
-                         hipStream_t stream);
+template <typename T>
+int lmi_quad_forward(const RayenPack* p, const LmiQuadImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                     T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream);
+template <typename T> bool lmi_quad_bwd_serves(const RayenPack* p, const LmiQuadImage* img);
+template <typename T>
+int lmi_quad_backward(const RayenPack* p, const LmiQuadImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                      const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream);
 
 // fp32 MFMA backward for sets with equalities / packed low-rank quadratics (rayen_mfma_bwdg.hip)
 // the same shapes with every quadratic in packed tiles, n <= 32: backward on f16 pairs (rayen_mfma_bwdp.hip)
@@ -313,72 +316,42 @@ int mfma64_bwdg_backward(const RayenPack* p, const Mfma64BwdgImage* img, const d
                          double* grad_v, int64_t ldgv, int old_mode, hipStream_t stream);
 
 // one wave per sample, the matrix in LDS: sets = [linear rows] + one LMI of any size the LDS holds (rayen_lmi_wave.h)
-bool lmi_wave_eligible_f32(const RayenPack* p);
-bool lmi_wave_eligible_f64(const RayenPack* p);
-int lmi_wave_build_f32(const RayenPack* p, LmiWaveImage** out, int64_t* bytes);
-int lmi_wave_build_f64(const RayenPack* p, LmiWaveImage** out, int64_t* bytes);
+template <typename T> bool lmi_wave_eligible(const RayenPack* p);
+template <typename T> int lmi_wave_build(const RayenPack* p, LmiWaveImage** out, int64_t* bytes);
 void lmi_wave_free(LmiWaveImage* img);
-int lmi_wave_forward_f32(const RayenPack* p, const LmiWaveImage* img, const float* v, int64_t B, int64_t ldv, float* y,
-                         int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream);
-int lmi_wave_forward_f64(const RayenPack* p, const LmiWaveImage* img, const double* v, int64_t B, int64_t ldv, double* y,
-                         int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream);
-int lmi_wave_backward_f32(const RayenPack* p, const LmiWaveImage* img, const float* v, int64_t B, int64_t ldv,
-                          const float* kappa, const int32_t* active, const float* grad_y, int64_t ldg, float* grad_v,
-                          int64_t ldgv, hipStream_t stream);
-int lmi_wave_backward_f64(const RayenPack* p, const LmiWaveImage* img, const double* v, int64_t B, int64_t ldv,
-                          const double* kappa, const int32_t* active, const double* grad_y, int64_t ldg, double* grad_v,
-                          int64_t ldgv, hipStream_t stream);
+template <typename T> bool lmi_wave_serves(const LmiWaveImage* img);      // (the image may exist for the block kernel alone)
+template <typename T>
+int lmi_wave_forward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                     T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream);
+template <typename T>
+int lmi_wave_backward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                      const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream);
 
 // one workgroup per sample, the packed lower triangle in LDS (rayen_lmi_block.h): forward and backward for r up to ~280 (fp32) / ~197 (fp64)
 // on the wave kernel's image
-bool lmi_block_eligible_f32(const RayenPack* p);
-bool lmi_block_eligible_f64(const RayenPack* p);
-bool lmi_block_serves_f32(const LmiWaveImage* img);
-bool lmi_block_serves_f64(const LmiWaveImage* img);
-int lmi_block_prepare_f32(const LmiWaveImage* img);
-int lmi_block_prepare_f64(const LmiWaveImage* img);
-bool lmi_block_eligible_mixed_f32(const RayenPack* p);     // ... with quadratics / cones next to the LMI
-bool lmi_block_eligible_mixed_f64(const RayenPack* p);
-int lmi_block_forward_f32(const RayenPack* p, const LmiWaveImage* img, const float* v, int64_t B, int64_t ldv, float* y,
-                          int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream,
-                          const float* kappa_in = nullptr, int64_t ldk_in = 1, int old_mode = 0);
-int lmi_block_forward_f64(const RayenPack* p, const LmiWaveImage* img, const double* v, int64_t B, int64_t ldv, double* y,
-                          int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream,
-                          const double* kappa_in = nullptr, int64_t ldk_in = 1, int old_mode = 0);
-bool lmi_block_bwd_serves_f32(const LmiWaveImage* img);
-bool lmi_block_bwd_serves_f64(const LmiWaveImage* img);
-int lmi_block_backward_f32(const RayenPack* p, const LmiWaveImage* img, const float* v, int64_t B, int64_t ldv,
-                           const float* kappa, const int32_t* active, const float* grad_y, int64_t ldg, float* grad_v,
-                           int64_t ldgv, hipStream_t stream, int only_lmi = 0, int old_mode = 0);
-int lmi_block_backward_f64(const RayenPack* p, const LmiWaveImage* img, const double* v, int64_t B, int64_t ldv,
-                           const double* kappa, const int32_t* active, const double* grad_y, int64_t ldg, double* grad_v,
-                           int64_t ldgv, hipStream_t stream, int only_lmi = 0, int old_mode = 0);
+template <typename T> bool lmi_block_eligible(const RayenPack* p);
+template <typename T> bool lmi_block_eligible_mixed(const RayenPack* p);     // ... with quadratics / cones next to the LMI
+template <typename T> bool lmi_block_serves(const LmiWaveImage* img);
+template <typename T> bool lmi_block_bwd_serves(const LmiWaveImage* img);
+template <typename T> int lmi_block_prepare(const LmiWaveImage* img);
+template <typename T>
+int lmi_block_forward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                      T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream, const T* kappa_in = nullptr,
+                      int64_t ldk_in = 1, int old_mode = 0);
+template <typename T>
+int lmi_block_backward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                       const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream,
+                       int only_lmi = 0, int old_mode = 0);
 // ... from the products T = v W_ext' of a library GEMM (sets with many generators): forward, and the backward's coefficients
-bool lmi_block_products_serves_f32(const LmiWaveImage* img);
-bool lmi_block_products_serves_f64(const LmiWaveImage* img);
-int lmi_block_forward_products_f32(const RayenPack* p, const LmiWaveImage* img, const float* prods, int64_t ldt, const float* v,
-                                   int64_t B, int64_t ldv, float* y, int64_t ldy, float* kappa, int32_t* active,
-                                   int32_t* nan_flag, hipStream_t stream);
-int lmi_block_forward_products_f64(const RayenPack* p, const LmiWaveImage* img, const double* prods, int64_t ldt, const double* v,
-                                   int64_t B, int64_t ldv, double* y, int64_t ldy, double* kappa, int32_t* active,
-                                   int32_t* nan_flag, hipStream_t stream);
-int lmi_block_bwd_coefficients_f32(const RayenPack* p, const LmiWaveImage* img, const float* prods, int64_t ldt, const float* v,
-                                   int64_t B, int64_t ldv, const float* kappa, const int32_t* active, const float* grad_y,
-                                   int64_t ldg, float* C, int64_t ldc, float* gs, hipStream_t stream);
-int lmi_block_bwd_coefficients_f64(const RayenPack* p, const LmiWaveImage* img, const double* prods, int64_t ldt, const double* v,
-                                   int64_t B, int64_t ldv, const double* kappa, const int32_t* active, const double* grad_y,
-                                   int64_t ldg, double* C, int64_t ldc, double* gs, hipStream_t stream);
-bool lmi_wave_serves_f32(const LmiWaveImage* img);      // (the image may exist for the block kernel alone)
-bool lmi_wave_serves_f64(const LmiWaveImage* img);
-
-bool lmi_quad_bwd_serves_f32(const RayenPack* p, const LmiQuadImage* img);
-bool lmi_quad_bwd_serves_f64(const RayenPack* p, const LmiQuadImage* img);
-int lmi_quad_backward_f32(const RayenPack* p, const LmiQuadImage* img, const float* v, int64_t B, int64_t ldv,
-                          const float* kappa, const int32_t* active, const float* grad_y, int64_t ldg,
-                          float* grad_v, int64_t ldgv, hipStream_t stream);
-int lmi_quad_backward_f64(const RayenPack* p, const LmiQuadImage* img, const double* v, int64_t B, int64_t ldv,
-                          const double* kappa, const int32_t* active, const double* grad_y, int64_t ldg,
-                          double* grad_v, int64_t ldgv, hipStream_t stream);
+template <typename T> bool lmi_block_products_serves(const LmiWaveImage* img);
+template <typename T>
+int lmi_block_forward_products(const RayenPack* p, const LmiWaveImage* img, const T* prods, int64_t ldt, const T* v, int64_t B,
+                               int64_t ldv, T* y, int64_t ldy, T* kappa, int32_t* active, int32_t* nan_flag,
+                               hipStream_t stream);
+template <typename T>
+int lmi_block_bwd_coefficients(const RayenPack* p, const LmiWaveImage* img, const T* prods, int64_t ldt, const T* v, int64_t B,
+                               int64_t ldv, const T* kappa, const int32_t* active, const T* grad_y, int64_t ldg, T* C,
+                               int64_t ldc, T* gs, hipStream_t stream);
 
 // fp64 MFMA backward (rayen_mfma_bwd64.hip)
 bool mfma64_bwd_eligible(const RayenPack* p);

@@ -1075,7 +1075,7 @@ Plan plan_for(int r, int n, bool bwd) {
   return p;
 }
 
-// (eligibility of a shape, rayen_lmi_block.hip)
+// (eligibility of a shape: lmi_block_eligible below)
 template <typename T>
 int head_cols_fwd(int r, int n) { const Plan p = plan_for<T>(r, n, false); return p.nth == 0 ? -1 : p.hc; }
 template <typename T>
@@ -1197,4 +1197,59 @@ int lmi_block_backward_t(const RayenPack* p, const LmiWaveImage* img, const T* v
 }
 
 }  // namespace lb
+
+// the interface of rayen_internal.h; instantiated for float and double in rayen_lmi_block.hip
+// [linear rows] + one LMI whose packed triangle fits the LDS
+template <typename T>
+bool lmi_block_eligible(const RayenPack* p) {
+  int n_lmi = 0, r = 0;
+  for (const RayenSegment& g : p->segs) {
+    if (g.type == RAYEN_SEG_LMI) { ++n_lmi; r = g.dim; }
+    else if (g.type != RAYEN_SEG_LIN) return false;
+  }
+  return n_lmi == 1 && r >= 2 && (lb::head_cols_fwd<T>(r, p->n) >= 0 || lb::head_cols_fwd<T>(r, 0) >= 0);   // (fused | products)
+}
+// the same with quadratics / cones next to the LMI (another kernel's: rayen_abi.hip::mixed_forward)
+template <typename T>
+bool lmi_block_eligible_mixed(const RayenPack* p) {
+  int n_lmi = 0, n_other = 0, r = 0;
+  for (const RayenSegment& g : p->segs) {
+    if (g.type == RAYEN_SEG_LMI) { ++n_lmi; r = g.dim; }
+    else if (g.type != RAYEN_SEG_LIN) ++n_other;
+  }
+  return n_lmi == 1 && n_other > 0 && r >= 2 && lb::head_cols_fwd<T>(r, p->n) >= 0 && lb::head_cols_bwd<T>(r, p->n) >= 0;
+}
+template <typename T> bool lmi_block_serves(const LmiWaveImage* img) { return lb::lmi_block_serves_t<T>(img); }
+template <typename T> bool lmi_block_bwd_serves(const LmiWaveImage* img) { return lb::lmi_block_bwd_serves_t<T>(img); }
+template <typename T> int lmi_block_prepare(const LmiWaveImage* img) { return lb::lmi_block_prepare_t<T>(img); }
+template <typename T>
+int lmi_block_forward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                      T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream, const T* kappa_in, int64_t ldk_in,
+                      int old_mode) {
+  return lb::lmi_block_forward_t<T>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, kappa_in, ldk_in, nullptr, 0, old_mode);
+}
+template <typename T>
+int lmi_block_backward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                       const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream,
+                       int only_lmi, int old_mode) {
+  return lb::lmi_block_backward_t<T>(p, img, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, stream, only_lmi, nullptr, 0, nullptr, 0,
+                                     nullptr, old_mode);
+}
+// the products route (sets with many generators): T = v W_ext' comes from a library GEMM, see rayen_abi.hip
+template <typename T> bool lmi_block_products_serves(const LmiWaveImage* img) {
+  return img != nullptr && lb::plan_for<T>(img->r, 0, false).nth != 0 && lb::plan_for<T>(img->r, 0, true).nth != 0;
+}
+template <typename T>
+int lmi_block_forward_products(const RayenPack* p, const LmiWaveImage* img, const T* prods, int64_t ldt, const T* v, int64_t B,
+                               int64_t ldv, T* y, int64_t ldy, T* kappa, int32_t* active, int32_t* nan_flag,
+                               hipStream_t stream) {
+  return lb::lmi_block_forward_t<T>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, nullptr, 1, prods, ldt);
+}
+template <typename T>
+int lmi_block_bwd_coefficients(const RayenPack* p, const LmiWaveImage* img, const T* prods, int64_t ldt, const T* v, int64_t B,
+                               int64_t ldv, const T* kappa, const int32_t* active, const T* grad_y, int64_t ldg, T* C,
+                               int64_t ldc, T* gs, hipStream_t stream) {
+  return lb::lmi_block_backward_t<T>(p, img, v, B, ldv, kappa, active, grad_y, ldg, nullptr, 0, stream, 0, prods, ldt, C, ldc, gs);
+}
+
 }  // namespace rayen

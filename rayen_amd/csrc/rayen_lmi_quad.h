@@ -936,7 +936,7 @@ int launch_quad_bwd(const RayenPack* p, const LmiQuadImage* img, const T* v, int
 
 // fp64 keeps a quarter of the matrix, the reflectors and the tridiagonal solve in registers only up to 16 x 16
 template <typename T>
-bool lmi_quad_bwd_serves(const RayenPack* p, const LmiQuadImage* img) {
+bool lmi_quad_bwd_serves_t(const RayenPack* p, const LmiQuadImage* img) {
   if (sizeof(T) == 8 && img->R > 24) return false;
   return quad_bwd_lds_bytes<T>(p, img->R, img->m) <= 128 * 1024;
 }
@@ -959,4 +959,24 @@ int lmi_quad_backward_t(const RayenPack* p, const LmiQuadImage* img, const T* v,
 }
 
 }  // namespace lq
+
+// the interface of rayen_internal.h; instantiated in rayen_lmi_quad32.hip (float) and rayen_lmi_quad64.hip (double)
+template <typename T> bool lmi_quad_eligible(const RayenPack* p) { return lq::lmi_quad_eligible_t<T>(p); }
+template <typename T> int lmi_quad_build(const RayenPack* p, LmiQuadImage** out, int64_t* bytes) {
+  return lq::lmi_quad_build_t<T>(p, out, bytes);
+}
+template <typename T>
+int lmi_quad_forward(const RayenPack* p, const LmiQuadImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                     T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream) {
+  return lq::lmi_quad_forward_t<T>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
+}
+template <typename T> bool lmi_quad_bwd_serves(const RayenPack* p, const LmiQuadImage* img) {
+  return lq::lmi_quad_bwd_serves_t<T>(p, img);
+}
+template <typename T>
+int lmi_quad_backward(const RayenPack* p, const LmiQuadImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                      const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream) {
+  return lq::lmi_quad_backward_t<T>(p, img, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, stream);
+}
+
 }  // namespace rayen

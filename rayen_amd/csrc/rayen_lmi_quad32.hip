@@ -3,15 +3,10 @@
 
 namespace rayen {
 
-bool lmi_quad_eligible_f32(const RayenPack* p) { return lq::lmi_quad_eligible_t<float>(p); }
-int lmi_quad_build_f32(const RayenPack* p, LmiQuadImage** out, int64_t* bytes) {
-  return lq::lmi_quad_build_t<float>(p, out, bytes);
-}
-int lmi_quad_forward_f32(const RayenPack* p, const LmiQuadImage* img, const float* v, int64_t B, int64_t ldv,
-                         float* y, int64_t ldy, float* kappa, int32_t* active, int32_t* nan_flag,
-                         hipStream_t stream) {
-  return lq::lmi_quad_forward_t<float>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
-}
+template bool lmi_quad_eligible<float>(const RayenPack*);
+template int lmi_quad_build<float>(const RayenPack*, LmiQuadImage**, int64_t*);
+template int lmi_quad_forward<float>(const RayenPack*, const LmiQuadImage*, const float*, int64_t, int64_t, float*, int64_t,
+                                     float*, int32_t*, int32_t*, hipStream_t);
 void lmi_quad_free(LmiQuadImage* img) {
   if (img == nullptr) return;
   if (img->data) (void)hipFree(img->data);
@@ -20,12 +15,8 @@ void lmi_quad_free(LmiQuadImage* img) {
   if (img->lin_id) (void)hipFree(img->lin_id);
   delete img;
 }
-
-bool lmi_quad_bwd_serves_f32(const RayenPack* p, const LmiQuadImage* img) { return lq::lmi_quad_bwd_serves<float>(p, img); }
-int lmi_quad_backward_f32(const RayenPack* p, const LmiQuadImage* img, const float* v, int64_t B, int64_t ldv,
-                          const float* kappa, const int32_t* active, const float* grad_y, int64_t ldg, float* grad_v,
-                          int64_t ldgv, hipStream_t stream) {
-  return lq::lmi_quad_backward_t<float>(p, img, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, stream);
-}
+template bool lmi_quad_bwd_serves<float>(const RayenPack*, const LmiQuadImage*);
+template int lmi_quad_backward<float>(const RayenPack*, const LmiQuadImage*, const float*, int64_t, int64_t, const float*,
+                                      const int32_t*, const float*, int64_t, float*, int64_t, hipStream_t);
 
 }  // namespace rayen

@@ -516,4 +516,22 @@ int lmi_wave_backward_t(const RayenPack* p, const LmiWaveImage* img, const T* v,
 }
 
 }  // namespace lw
+
+// the interface of rayen_internal.h; instantiated in rayen_lmi_wave32.hip (float) and rayen_lmi_wave64.hip (double)
+template <typename T> bool lmi_wave_eligible(const RayenPack* p) { return lw::lmi_wave_eligible_t<T>(p); }
+template <typename T> int lmi_wave_build(const RayenPack* p, LmiWaveImage** out, int64_t* bytes) {
+  return lw::lmi_wave_build_t<T>(p, out, bytes);
+}
+template <typename T> bool lmi_wave_serves(const LmiWaveImage* img) { return lw::lmi_wave_serves_t<T>(img); }
+template <typename T>
+int lmi_wave_forward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, T* y, int64_t ldy,
+                     T* kappa, int32_t* active, int32_t* nan_flag, hipStream_t stream) {
+  return lw::lmi_wave_forward_t<T>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, stream);
+}
+template <typename T>
+int lmi_wave_backward(const RayenPack* p, const LmiWaveImage* img, const T* v, int64_t B, int64_t ldv, const T* kappa,
+                      const int32_t* active, const T* grad_y, int64_t ldg, T* grad_v, int64_t ldgv, hipStream_t stream) {
+  return lw::lmi_wave_backward_t<T>(p, img, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, stream);
+}
+
 }  // namespace rayen

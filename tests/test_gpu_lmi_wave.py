@@ -217,6 +217,29 @@ def test_wave_kernel_small_and_ragged_batches_and_nan_rows(kernel, monkeypatch):
     assert torch.equal(yb[keep], y_all[keep])
 
 
+@pytest.mark.parametrize("dtype,r,pin", [(torch.float64, 44, "0"), (torch.float64, 45, "1"), (torch.float32, 33, "1")])
+def test_default_choice_between_the_wave_and_the_block_kernel(dtype, r, pin, monkeypatch):
+    """Without RAYEN_LMI_BLOCK the library chooses (rayen_abi.hip::lmi_block_preferred): in fp64 the wave kernel up to
+    44 x 44 and the workgroup kernel beyond, in fp32 the workgroup kernel wherever it serves.  Both kernels are correct, so
+    no comparison with the oracle sees a backward that moved to the other one: the default is compared bit for bit with
+    the same call under the pin it should equal, and the forward names its kernel."""
+    monkeypatch.delenv("RAYEN_LMI_BLOCK", raising=False)
+    cs, layer = _layer(_case(k=4, r=r, m=0, n_eq=0, seed=50 + r), dtype)
+    dp, _ = layer.device_pack(torch.device("cuda", 0))
+    gen = torch.Generator().manual_seed(r)
+    xd = torch.empty(8, cs.n).uniform_(-2.0, 2.0, generator=gen).to(dtype).cuda()
+    g = torch.empty(8, cs.k).uniform_(-1.0, 1.0, generator=gen).to(dtype).cuda()
+    y, kappa, active = ops.project_raw(xd, dp, want_active=True)
+    fam = _lib.load().rayen_last_forward_kernel()
+    assert fam == (_lib.KERNEL_LMI_BLOCK if pin == "1" else _lib.KERNEL_LMI_WAVE), (r, fam)
+    grad = ops.backward_raw(xd, kappa, active, g, dp)
+    monkeypatch.setenv("RAYEN_LMI_BLOCK", pin)
+    y_pin, kappa_pin, active_pin = ops.project_raw(xd, dp, want_active=True)
+    assert _lib.load().rayen_last_forward_kernel() == fam
+    assert torch.equal(y_pin, y) and torch.equal(kappa_pin, kappa) and torch.equal(active_pin, active)
+    assert torch.equal(ops.backward_raw(xd, kappa, active, g, dp), grad)
+
+
 MANY = {
     "r50_k160_lin_eq": dict(k=160, r=50, m=10, n_eq=2, seed=31),      # NA_E != I: its products ride behind the rows of W
     "r120_k200": dict(k=200, r=120, m=0, n_eq=0, seed=32),
