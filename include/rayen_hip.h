@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 10
+#define RAYEN_ABI_VERSION 11
 
 enum {
   RAYEN_OK = 0,
@@ -396,6 +396,50 @@ int rayen_dc3_backward_f32(const RayenDc3Pack* pack, const float* q, int64_t B, 
 int rayen_dc3_backward_f64(const RayenDc3Pack* pack, const double* q, int64_t B, int64_t ldq, const double* grad_y,
                            int64_t ldg, double* grad_q, int64_t ldgq, double lr, double momentum, int32_t max_steps,
                            const int32_t* tstar, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- Euclidean projection onto the set (ABI v11): the core of the reference's PP / UP layers
+ * (rayen/constraint_module.py:76-96 and :488-504), batched and differentiable
+ *
+ * The program min ||z - q||^2 s.t. G z + h in K, z in R^n, with K = m_lin orthant rows followed by n_soc second-order cones
+ * of soc_rows[c] rows each (||rows but the last|| <= the last), m rows in all.  The caller assembles and equilibrates the
+ * rows (rayen_amd/projection.py) and passes Kinv = ((2 + sigma) I + rho G'G)^-1 [n, n] and w0 = -rho G'h [n]; everything is
+ * fp64, row-major, read at creation; the pack is immutable afterwards and holds an fp32 and an fp64 device image.  One
+ * iteration on a sample's state (x [n], v [m]), from x = q, v = Pi_K(G q + h):
+ *     p = Pi_K(v),  xt = Kinv (sigma x + 2 q + w0 + rho G'(2 p - v)),  r = G xt + h - p,
+ *     x <- x + alpha (xt - x),  v <- v + alpha r
+ * A row stops, answering xt, when max|r| <= eps (1 + max|p|) and max|xt - x| <= eps (1 + max|xt|), or at max_iters; the
+ * stop is PER ROW.  A row with G q + h in K answers q and iters = 0.
+ *
+ * The kernels keep one sample per wave, x in lanes (n <= 64), v in at most 9 registers per lane (m <= 576), the cones in the
+ * argument block (n_soc <= 32) and G', Kinv, h, w0 plus 4 (128 + m) elements of scratch in LDS: a shape beyond any of
+ * these, or over 160 KiB - 256 B of LDS at the element size asked for, returns RAYEN_E_UNSUPPORTED from the forward and the
+ * backward (the pack is still created).
+ *
+ * forward: q [B, ldq] (first n columns read), z [B, ldz] (first n columns written), iters [B] (iterations each row took;
+ *   max_iters: the row did not meet the stop rule), vstar [B, m] (the v each row stopped at: the backward's input).  ws:
+ *   scratch of at least rayen_proj_workspace_bytes(pack, B, f64, 0) bytes, 16-byte aligned.  The iterations run in
+ *   launches of 32 with finished rows idle (no host sync: capturable in a graph).
+ * backward: grad_q = J g per row, J the (symmetric) Jacobian of the projection at the forward's fixed point, by the
+ *   linearised iteration at vstar run to the same stop rule on g / max|g|; g [B, ldg], grad_q [B, ldgq] (first n columns).
+ *   ws: at least rayen_proj_workspace_bytes(.., 1) bytes.  eps and max_iters need not be the forward's. */
+typedef struct RayenProjPack RayenProjPack;
+int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv, const double* w0, int32_t n, int32_t m,
+                           int32_t m_lin, const int32_t* soc_rows, int32_t n_soc, double rho, double sigma, double alpha,
+                           RayenProjPack** out);
+void rayen_proj_pack_destroy(RayenProjPack* pack);
+int64_t rayen_proj_workspace_bytes(const RayenProjPack* pack, int64_t B, int32_t f64, int32_t backward);
+int rayen_proj_forward_f32(const RayenProjPack* pack, const float* q, int64_t B, int64_t ldq, float* z, int64_t ldz,
+                           int32_t* iters, float* vstar, double eps, int32_t max_iters, void* ws, int64_t ws_bytes,
+                           void* stream);
+int rayen_proj_forward_f64(const RayenProjPack* pack, const double* q, int64_t B, int64_t ldq, double* z, int64_t ldz,
+                           int32_t* iters, double* vstar, double eps, int32_t max_iters, void* ws, int64_t ws_bytes,
+                           void* stream);
+int rayen_proj_backward_f32(const RayenProjPack* pack, const float* g, int64_t B, int64_t ldg, const float* vstar,
+                            const int32_t* iters, float* grad_q, int64_t ldgq, double eps, int32_t max_iters, void* ws,
+                            int64_t ws_bytes, void* stream);
+int rayen_proj_backward_f64(const RayenProjPack* pack, const double* g, int64_t B, int64_t ldg, const double* vstar,
+                            const int32_t* iters, double* grad_q, int64_t ldgq, double eps, int32_t max_iters, void* ws,
+                            int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

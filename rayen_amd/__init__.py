@@ -8,6 +8,7 @@ Drop-in for the hot path of leggedrobotics/rayen: ``ConstraintModule.forward`` w
 """
 from . import constraints, utils  # noqa: F401
 from . import constraint_module  # noqa: F401
+from . import projection  # noqa: F401
 
-__all__ = ["constraints", "constraint_module", "utils"]
+__all__ = ["constraints", "constraint_module", "projection", "utils"]
 __version__ = "0.1.0"

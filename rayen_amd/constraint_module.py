@@ -20,8 +20,8 @@ is free; ``'Bar'`` (the barycentric baseline, :124-132 and :479-486) converts th
 vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kernel per direction
 (``rayen_amd/csrc/rayen_bar.hip``); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
 quadratic sets only) needs ``args_DC3`` and runs its fixed iteration, batch-global stop included, on
-``rayen_amd/csrc/rayen_dc3.hip`` (host side: ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) need a conic
-solver inside the layer, which this package does not carry, and raise ``NotImplementedError``.
+``rayen_amd/csrc/rayen_dc3.hip`` (host side: ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
+``NotImplementedError`` here: they are served by a module of their own, ``rayen_amd.projection.ProjectionModule``.
 
 Documented deviation: for an SOC whose ray never meets the cone (negative
 discriminant with ``c' < 0``) the reference's assert at :342 fires (or NaN under

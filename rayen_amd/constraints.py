@@ -584,6 +584,35 @@ class ConvexConstraints:
             raise Exception(f"Value is not optimal, prob_status={info['status']}")
         return y.reshape(k, 1), float(np.sum((y - p) ** 2))
 
+    def projectBatch(self, Y, max_iters=4000, eps=None):
+        """Batched :meth:`project`: ``Y [B, k]`` -> ``(Y_projected [B, k], squared distances [B])``.  A torch tensor stays
+        on its device and dtype (a HIP device runs ``rayen_amd/csrc/rayen_proj.hip``); anything else is computed in fp64
+        on the host and returned as numpy.  The point is split into its part in the equality subspace,
+        ``z = NA_E'(y - yp)``, which ``projection.ProjectionModule.project`` projects, and the part orthogonal to it,
+        whose squared norm adds to the distance (``NA_E`` has orthonormal columns).  ``eps``: the stop tolerance of the
+        iteration (default 1e-9 in fp64, 1e-6 below)."""
+        import torch
+        from . import projection
+        as_numpy = not isinstance(Y, torch.Tensor)
+        Yt = torch.as_tensor(np.asarray(Y, dtype=np.float64)) if as_numpy else Y
+        Yt = Yt.reshape(-1, self.k)
+        module = self.__dict__.get("_projection_module")
+        if module is None:
+            module = self.__dict__["_projection_module"] = projection.ProjectionModule(self, create_map=False)
+        if eps is None:
+            eps = 1e-9 if Yt.dtype == torch.float64 else 1e-6
+        NA_E = torch.as_tensor(self.NA_E, dtype=Yt.dtype, device=Yt.device)
+        yp = torch.as_tensor(self.yp, dtype=Yt.dtype, device=Yt.device).reshape(1, -1)
+        with torch.no_grad():
+            zin = (Yt - yp) @ NA_E
+            off = Yt - (zin @ NA_E.T + yp)
+            z, _ = module.project(zin, max_iters=max_iters, eps=eps)
+            out = z @ NA_E.T + yp
+            dist = ((z - zin) ** 2).sum(dim=1) + (off ** 2).sum(dim=1)
+        if as_numpy:
+            return out.numpy(), dist.numpy()
+        return out, dist
+
     def getViolation(self, y_to_be_projected):
         """Squared distance of a point to the set (constraints.py:549-559); 0 for feasible points."""
         if y_to_be_projected.ndim == 1:

@@ -678,3 +678,144 @@ def _dc3_backward(ctx, grad_y, grad_steps):
 
 
 dc3_project.register_autograd(_dc3_backward, setup_context=_dc3_setup_context)
+
+
+# ------------------------------------------------------------------------------------------------
+# Euclidean projection onto the set (the PP / UP baselines, rayen_amd/projection.py) on rayen_proj.hip
+# ------------------------------------------------------------------------------------------------
+
+# v* [B, m] plus the state between launches; beyond this the op refuses (split the batch)
+PROJ_MAX_WORKSPACE_BYTES = 8 << 30
+
+
+class ProjPack:
+    """Owner of one ``RayenProjPack*``: fp32 and fp64 images of a ``projection.Program`` on one device.  Immutable, so a
+    captured graph may keep using it."""
+
+    def __init__(self, arrays, device_index):
+        a = arrays
+        self.n, self.m = int(a["n"]), int(a["m"])
+        self.device_index = int(device_index)
+        handle = ctypes.c_void_p()
+        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+        with torch.cuda.device(self.device_index):
+            _lib.check(_lib.load().rayen_proj_pack_create(
+                ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]), ptr(a["w0"]), self.n, self.m, int(a["m_lin"]),
+                ptr(a["soc_rows"]), int(a["soc_rows"].size), float(a["rho"]), float(a["sigma"]), float(a["alpha"]),
+                ctypes.byref(handle)), "rayen_proj_pack_create")
+        self.handle = handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.load().rayen_proj_pack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _proj_check(q, pack, what="q"):
+    if not q.is_cuda:
+        raise RuntimeError("rayen_amd: the projection's HIP op runs on an MI355X (HIP) device only; got a "
+                           f"{q.device} tensor")
+    if q.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
+    if q.dim() != 2 or q.shape[1] < pack.n:
+        raise RuntimeError(f"rayen_amd: expected {what} of shape [B, >= {pack.n}], got {tuple(q.shape)}")
+    if q.device.index != pack.device_index:
+        raise RuntimeError("rayen_amd: input and projection pack live on different devices")
+
+
+def _proj_workspace(pack, q, backward):
+    nbytes = int(_lib.load().rayen_proj_workspace_bytes(pack.handle, q.shape[0], int(q.dtype == torch.float64),
+                                                        int(backward)))
+    if nbytes < 0:
+        raise RuntimeError("rayen_amd: rayen_proj_workspace_bytes refused its arguments")
+    total = nbytes + q.shape[0] * pack.m * q.element_size()
+    if total > PROJ_MAX_WORKSPACE_BYTES:
+        raise RuntimeError(f"rayen_amd: the projection {'backward' if backward else 'forward'} of {q.shape[0]} rows x "
+                           f"{pack.m} cone rows needs {total} bytes of scratch, more than ops.PROJ_MAX_WORKSPACE_BYTES = "
+                           f"{PROJ_MAX_WORKSPACE_BYTES}; split the batch")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device), nbytes
+
+
+def proj_forward_raw(q, pack, max_iters, eps):
+    """``(z [B, n], iters [B] int32, vstar [B, m])`` through ``rayen_proj_forward_*``."""
+    _proj_check(q, pack)
+    q = _dense_rows(q, pack.n)
+    B = q.shape[0]
+    z = torch.empty((B, pack.n), dtype=q.dtype, device=q.device)
+    iters = torch.empty((B,), dtype=torch.int32, device=q.device)
+    vstar = torch.empty((B, pack.m), dtype=q.dtype, device=q.device)
+    with _on_device(q.device):
+        ws, nbytes = _proj_workspace(pack, q, False)
+        code = _entry("rayen_proj_forward_f32" if q.dtype == torch.float32 else "rayen_proj_forward_f64")(
+            pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(z), pack.n, _ptr(iters), _ptr(vstar),
+            float(eps), int(max_iters), _ptr(ws), nbytes, _stream(q.device.index))
+    _lib.check(code, "rayen_proj_forward")
+    return z, iters, vstar
+
+
+def proj_backward_raw(grad_z, vstar, iters, pack, max_iters, eps):
+    """``grad_q [B, n] = J grad_z`` row by row through ``rayen_proj_backward_*``."""
+    _proj_check(grad_z, pack, "grad_z")
+    g = _dense_rows(grad_z, pack.n)
+    vstar, iters = vstar.contiguous(), iters.contiguous()
+    B = g.shape[0]
+    grad_q = torch.empty((B, pack.n), dtype=g.dtype, device=g.device)
+    with _on_device(g.device):
+        ws, nbytes = _proj_workspace(pack, g, True)
+        code = _entry("rayen_proj_backward_f32" if g.dtype == torch.float32 else "rayen_proj_backward_f64")(
+            pack.handle, _ptr(g), B, g.stride(0) if B else pack.n, _ptr(vstar), _ptr(iters), _ptr(grad_q), pack.n,
+            float(eps), int(max_iters), _ptr(ws), nbytes, _stream(g.device.index))
+    _lib.check(code, "rayen_proj_backward")
+    return grad_q
+
+
+@torch.library.custom_op("rayen_amd::euclid_project", mutates_args=())
+def euclid_project(q: torch.Tensor, pack_id: int, max_iters: int,
+                   eps: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(z [B, n], iters [B] int32, vstar [B, m])``: the Euclidean projection on torch's current stream."""
+    return proj_forward_raw(q, _pack(pack_id), max_iters, eps)
+
+
+@euclid_project.register_fake
+def _(q, pack_id, max_iters, eps):
+    pack = _pack(pack_id)
+    B = q.shape[0]
+    return q.new_empty((B, pack.n)), q.new_empty((B,), dtype=torch.int32), q.new_empty((B, pack.m))
+
+
+@torch.library.custom_op("rayen_amd::euclid_project_bwd", mutates_args=())
+def euclid_project_bwd(grad_z: torch.Tensor, vstar: torch.Tensor, iters: torch.Tensor, pack_id: int, max_iters: int,
+                       eps: float) -> torch.Tensor:
+    return proj_backward_raw(grad_z, vstar, iters, _pack(pack_id), max_iters, eps)
+
+
+@euclid_project_bwd.register_fake
+def _(grad_z, vstar, iters, pack_id, max_iters, eps):
+    return grad_z.new_empty((grad_z.shape[0], _pack(pack_id).n))
+
+
+def _proj_setup_context(ctx, inputs, output):
+    q, pack_id, max_iters, eps = inputs
+    ctx.pack_id, ctx.max_iters, ctx.eps, ctx.width = pack_id, max_iters, eps, q.shape[1]
+    ctx.save_for_backward(output[2], output[1])
+
+
+def _proj_backward(ctx, grad_z, grad_iters, grad_vstar):
+    vstar, iters = ctx.saved_tensors
+    if grad_z is None:
+        return None, None, None, None
+    pack = _pack(ctx.pack_id)
+    grad_q = torch.ops.rayen_amd.euclid_project_bwd(grad_z.to(vstar.dtype), vstar, iters, ctx.pack_id, ctx.max_iters,
+                                                    ctx.eps)
+    if ctx.width > pack.n:          # columns of q beyond n are not read
+        grad_q = torch.nn.functional.pad(grad_q, (0, ctx.width - pack.n))
+    return grad_q, None, None, None
+
+
+euclid_project.register_autograd(_proj_backward, setup_context=_proj_setup_context)

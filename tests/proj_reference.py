@@ -1,0 +1,392 @@
+"""fp64 reference, seeded cases and helpers for the Euclidean-projection kernels (rayen_amd/csrc/rayen_proj.hip).
+
+Forward reference: ``rayen_amd.conic.solve`` row by row at ``eps_abs = eps_rel = 1e-11`` on the program assembled HERE from
+the set (unequilibrated rows; the solver balances ``rho`` every 100 iterations and stops on the OSQP residuals): another
+implementation than the fixed-``rho`` iteration of rayen_amd/projection.py and its kernels.
+
+Backward reference: the KKT Jacobian of the projection at the reference solution, in numpy, from the ORIGINAL constraint
+functions ``g_i(z) <= 0`` (rows of ``A_p``; ``1/2 y'Py + q'y + r`` and ``||My + s|| - c'y - d`` at ``y = NA_E z + yp``), not
+from the cone rows and not from the linearised iteration (that derivation is what the tests judge):
+
+    active a = {i : g_i(z*) >= -ACTIVE_TOL},  lambda = argmin ||z* - q + J_a' lambda||,  H = I + sum_a lambda_i hess g_i
+    J = H^-1 - H^-1 J_a' (J_a H^-1 J_a')^-1 J_a H^-1
+
+``served`` restates the kernel's rule; the case table names each case for what it exercises.
+"""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+from rayen_amd import conic, constraints, workloads
+
+KINK_FACTOR = 4.0                    # the project's margin on a measured rounding gap (tests/dc3_reference.py)
+ACTIVE_TOL = 1e-7                    # g_i >= -ACTIVE_TOL at the reference solution: active
+KINK_MARGIN = 1e-4                   # a row whose smallest active multiplier or inactive slack is below this is a kink row
+LDS_LIMIT = 160 * 1024 - 256         # bytes a workgroup may use (rayen_proj.hip: kLdsBudget - 256)
+WAVES, MAX_ROWS, MAX_SOC, MAX_N = 4, 576, 32, 64
+BATCHES = (1, 65, 257)
+BATCH = 257                          # the seeded batch; the smaller ones are its leading rows
+CHUNK = 32                           # iterations per launch (rayen_proj.hip: kChunk)
+
+
+def kink_cap(B):
+    """``dc3_reference.kink_cap``: rows a backward comparison may leave out."""
+    return max(2, int(0.02 * B))
+
+
+def round4(x):
+    return (x + 3) & ~3
+
+
+def lds_bytes(n, m, elem):
+    """Bytes of LDS a workgroup of the kernel uses (restates rayen_proj.hip: dims_of + the waves' scratch)."""
+    mpad = m | 1
+    image = round4(n * mpad) + round4(n * n) + round4(m) + round4(n)
+    return (image + WAVES * (128 + round4(m))) * elem
+
+
+def served(n, m, n_soc, elem):
+    return 1 <= n <= MAX_N and 1 <= m <= MAX_ROWS and n_soc <= MAX_SOC and lds_bytes(n, m, elem) <= LDS_LIMIT
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# cases
+# ------------------------------------------------------------------------------------------------------------------
+
+# name, builder of the raw set, amp (inputs are z0 + amp N(0, I)).  Measured on the host (fp64 mirror against the
+# reference; fp32 mirror against the reference; iterations of the fp64 mirror at fixed rho, eps = 1e-9 / 1e-6): the figures
+# are in profiles/bench/proj_iterations.txt and beside each case in GAPS below.
+Case = namedtuple("Case", "name raw amp seed", defaults=(0,))
+
+
+def _raw_half_line():
+    raw = workloads._empty(1)
+    raw["A1"], raw["b1"] = np.array([[1.0]]), np.array([[1.0]])
+    return raw
+
+
+def _raw_ball():
+    raw = workloads._empty(4)
+    raw["P"], raw["q"], raw["r"] = [2.0 * np.eye(4)], [np.zeros((4, 1))], [np.array([[-1.0]])]      # ||y||^2 <= 1
+    return raw
+
+
+def _raw_cone():
+    raw = workloads._empty(3)
+    raw["M"], raw["s"] = [np.eye(3)[:2]], [np.zeros((2, 1))]
+    raw["c"], raw["d"] = [np.array([[0.0], [0.0], [1.0]])], [np.zeros((1, 1))]                    # ||(y1, y2)|| <= y3
+    raw["y0"] = np.array([[0.0], [0.0], [1.0]])
+    return raw
+
+
+def _raw_ragged():
+    """k = 8, three equalities (n = 5), 5 rows, one quadratic of rank 3 < n, one SOC with a 4-row M."""
+    rng = np.random.default_rng(85)
+    raw = workloads._empty(8)
+    raw["A1"], raw["b1"] = rng.uniform(-1, 1, (5, 8)), rng.uniform(0.3, 1.0, (5, 1))
+    raw["A2"], raw["b2"] = rng.uniform(-1, 1, (3, 8)), np.zeros((3, 1))
+    T = rng.uniform(-1, 1, (8, 3))
+    raw["P"], raw["q"], raw["r"] = [T @ T.T], [rng.uniform(-1, 1, (8, 1))], [np.array([[-0.5]])]
+    s = rng.uniform(-1, 1, (4, 1))
+    raw["M"], raw["s"] = [rng.uniform(-1, 1, (4, 8))], [s]
+    raw["c"], raw["d"] = [rng.uniform(-1, 1, (8, 1))], [np.linalg.norm(s) + np.array([[0.5]])]
+    return raw
+
+
+def _rlqs(k, m, nq, ns, seed=0):
+    return lambda: workloads.random_lin_quad_soc(k, m, nq, ns, seed=seed)
+
+
+CASES = [
+    Case("n1_one_inequality", _raw_half_line, 1.5),                  # the smallest program: one orthant row
+    Case("n3_box", workloads.cube, 0.6),                             # orthant rows only; faces, edges and corners
+    Case("n4_ball_quadratic_only", _raw_ball, 0.6),                  # no orthant row (m_lin = 0): the cones start at row 0
+    Case("n3_one_soc_only", _raw_cone, 1.0),                         # a true cone: apex region, mid region, inside
+    Case("k8_n5_ragged_equalities", _raw_ragged, 0.5),               # NA_E != I, rank-deficient quadratic, odd row counts
+    Case("n16_four_quadratics", _rlqs(16, 5, 4, 0, seed=3), 0.15),   # several cones active at once
+    Case("n32_full", _rlqs(32, 48, 3, 1, seed=4), 0.1),              # every family, half the lanes
+    Case("n33_padding_lanes", _rlqs(33, 6, 1, 1, seed=5), 0.15),     # n just past 32: lanes 33..63 idle
+    Case("n64_c3_shape", lambda: workloads.make_raw("c3"), 0.02),    # config 3: 522 cone rows, 9 rows per lane, 159 KiB
+]
+CASE = {c.name: c for c in CASES}
+
+# (n, cone rows m, cones) of each case's program: what served() is asked with (tests/test_proj_reference_host.py holds
+# them against the programs themselves)
+SHAPE = {"n1_one_inequality": (1, 1, 0), "n3_box": (3, 6, 0), "n4_ball_quadratic_only": (4, 6, 1),
+         "n3_one_soc_only": (3, 3, 1), "k8_n5_ragged_equalities": (5, 15, 2), "n16_four_quadratics": (16, 77, 4),
+         "n32_full": (32, 183, 4), "n33_padding_lanes": (33, 75, 2), "n64_c3_shape": (64, 522, 6)}
+
+# orthant rows only at n = 64: the largest image the kernel stages in fp32, and the first it refuses
+LDS_AT_LIMIT = Case("lds_at_the_limit", None, 0.1)
+LDS_JUST_OVER = Case("lds_just_over", None, 0.1)
+
+
+def lds_limit_rows(n=64, elem=4):
+    """(largest m served, smallest m refused) for linear rows only."""
+    m = 1
+    while served(n, m + 1, 0, elem):
+        m += 1
+    return m, m + 1
+
+
+@functools.lru_cache(maxsize=None)
+def make_cs(name):
+    if name in (LDS_AT_LIMIT.name, LDS_JUST_OVER.name):
+        m = lds_limit_rows()[name == LDS_JUST_OVER.name]
+        raw = workloads.random_lin_quad_soc(64, m, 0, 0, seed=6)
+    else:
+        raw = CASE[name].raw()
+    return workloads.build_constraints(raw)
+
+
+def _f32(x):
+    return np.ascontiguousarray(np.asarray(x, dtype=np.float64).astype(np.float32).astype(np.float64))
+
+
+def case_of(name):
+    return CASE.get(name) or {LDS_AT_LIMIT.name: LDS_AT_LIMIT, LDS_JUST_OVER.name: LDS_JUST_OVER}[name]
+
+
+@functools.lru_cache(maxsize=None)
+def make_inputs(name, B=BATCH):
+    """``(q [B, n], gy [B, k])``, fp64 arrays of fp32-representable values; a smaller batch is the leading rows.
+    ``q = z0 + amp u N(0, I)`` with ``u`` uniform in (0, 1.5) per row, so that every batch has rows at every depth."""
+    cs = make_cs(name)
+    rng = np.random.default_rng([cs.n, cs.k, len(name), 7, case_of(name).seed])
+    q = cs.z0.reshape(1, -1) + case_of(name).amp * rng.uniform(0.0, 1.5, (BATCH, 1)) * rng.standard_normal((BATCH, cs.n))
+    gy = rng.standard_normal((BATCH, cs.k))
+    return _f32(q)[:B], _f32(gy)[:B]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# forward reference
+# ------------------------------------------------------------------------------------------------------------------
+
+def reference_program(cs):
+    prog = conic.ConeProgram(cs.n)
+    prog.add(conic.NONNEG, -cs.A_p, cs.b_p[:, 0])
+    cs._nonlinear_cone_rows(prog, cs.NA_E, cs.yp)
+    return prog
+
+
+def project_rows(cs, q):
+    """``z* [B, n]`` by ``conic.solve`` per row at 1e-11."""
+    prog = reference_program(cs)
+    out = np.empty_like(q)
+    P = 2.0 * np.eye(cs.n)
+    for b in range(q.shape[0]):
+        z, info = conic.solve(prog, P, -2.0 * q[b], x0=q[b], eps_abs=1e-11, eps_rel=1e-11, max_iter=50000)
+        assert info["status"] == "solved", (b, info)
+        out[b] = z
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# backward reference
+# ------------------------------------------------------------------------------------------------------------------
+
+def constraint_values(cs, z):
+    """``g [c]`` of the original constraints at ``z [n]`` (<= 0 inside)."""
+    y = cs.NA_E @ z.reshape(-1, 1) + cs.yp
+    out = [(cs.A_p @ z.reshape(-1, 1) - cs.b_p).ravel()]
+    for qc in cs.qcs:
+        out.append((0.5 * y.T @ qc.P @ y + qc.q.T @ y + qc.r).ravel())
+    for soc in cs.socs:
+        out.append((np.linalg.norm(soc.M @ y + soc.s) - (soc.c.T @ y + soc.d)).ravel())
+    return np.concatenate(out)
+
+
+APEX_TOL = 1e-6                      # ||My + s|| below this at the solution: the row sits on the apex of that cone
+
+
+def constraint_derivatives(cs, z, index):
+    """``(rows [c, n], hessian [n, n], apex)`` of constraint ``index`` at ``z``: its gradient as one row, or, on the apex
+    of a cone (where ``(My + s, c'y + d) = 0`` and the constraint acts as that affine set), the rows ``-[M; c'] NA_E``
+    whose multipliers ``(mu_u, mu_t)`` live in the cone itself."""
+    n, N = cs.n, cs.NA_E
+    m = cs.A_p.shape[0]
+    if index < m:
+        return cs.A_p[index:index + 1].copy(), np.zeros((n, n)), False
+    y = N @ z.reshape(-1, 1) + cs.yp
+    index -= m
+    if index < len(cs.qcs):
+        qc = cs.qcs[index]
+        Ps = 0.5 * (qc.P + qc.P.T)
+        return (N.T @ (Ps @ y + qc.q)).reshape(1, n), N.T @ Ps @ N, False
+    soc = cs.socs[index - len(cs.qcs)]
+    u = soc.M @ y + soc.s
+    nu = float(np.linalg.norm(u))
+    MN = soc.M @ N
+    if nu <= APEX_TOL:
+        return -np.concatenate((MN, soc.c.T @ N), axis=0), np.zeros((n, n)), True
+    uh = u / nu
+    return (MN.T @ uh - N.T @ soc.c).reshape(1, n), MN.T @ (np.eye(u.shape[0]) - uh @ uh.T) @ MN / nu, False
+
+
+def jacobian_row(cs, q, z):
+    """``(J [n, n], margin)``: the Jacobian of the projection at ``q`` (solution ``z``) and the distance of the row from a
+    kink: the smallest of the active multipliers (on an apex: ``mu_t - ||mu_u||``) and the inactive slacks (``inf`` for
+    an interior row)."""
+    n = cs.n
+    g = constraint_values(cs, z)
+    active = np.flatnonzero(g >= -ACTIVE_TOL)
+    slack = -g[g < -ACTIVE_TOL]
+    margin = float(slack.min()) if slack.size else np.inf
+    if active.size == 0 or float(np.max(np.abs(q - z))) <= ACTIVE_TOL:
+        if active.size:                  # on the boundary with a zero step: multipliers 0
+            margin = 0.0
+        return np.eye(n), margin
+    parts = [constraint_derivatives(cs, z, int(i)) for i in active]
+    Ja = np.concatenate([p[0] for p in parts], axis=0)
+    lam = np.linalg.lstsq(Ja.T, q - z, rcond=None)[0]
+    H, at = np.eye(n), 0
+    for rows, hess, apex in parts:
+        l = lam[at:at + rows.shape[0]]
+        at += rows.shape[0]
+        if apex:
+            margin = min(margin, float(l[-1] - np.linalg.norm(l[:-1])))
+        else:
+            margin = min(margin, float(l[0]))
+            H = H + l[0] * hess
+    Hi = np.linalg.inv(H)
+    S = Ja @ Hi @ Ja.T
+    J = Hi - Hi @ Ja.T @ np.linalg.pinv(S, rcond=1e-10) @ Ja @ Hi
+    return J, margin
+
+
+Reference = namedtuple("Reference", "q gy z grad_q margin kink interior")
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """The seeded batch of ``name`` solved once: ``z``, ``grad_q = J NA_E' gy``, the kink margins."""
+    cs = make_cs(name)
+    q, gy = make_inputs(name)
+    z = project_rows(cs, q)
+    gz = gy @ cs.NA_E
+    grad = np.empty_like(q)
+    margin = np.empty(q.shape[0])
+    for b in range(q.shape[0]):
+        J, margin[b] = jacobian_row(cs, q[b], z[b])
+        grad[b] = J @ gz[b]
+    interior = np.array([float(np.max(constraint_values(cs, q[b]))) <= 0.0 for b in range(q.shape[0])])
+    for r in (z, grad, margin, interior):
+        r.setflags(write=False)
+    return Reference(q, gy, z, grad, margin, margin < KINK_MARGIN, interior)
+
+
+def row_gap(a, ref):
+    """Per row: max |a - ref| over (1 + max |ref|)."""
+    a, ref = np.asarray(a, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    return np.max(np.abs(a - ref), axis=1) / (1.0 + np.max(np.abs(ref), axis=1))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the host mirror on the seeded batches, and the bars made of it
+# ------------------------------------------------------------------------------------------------------------------
+
+# Stop tolerance and iteration limit the tests run each precision with (fp64: the issue's 1e-9).
+EPS = {"float64": 1e-9, "float32": 1e-6}
+MAX_ITERS = 2048
+FP64_CAP = 1e-6                      # the fp64 bar is never looser than this
+
+# Measured on the host, seeded batch of 257 rows, row_gap against the reference (forward / backward on non-kink rows) and
+# iterations (max / mean) of the fp64 mirror at fixed rho; the device's counts are in profiles/bench/proj_iterations.txt.
+#   case                      rho   fp64 eps 1e-9: fwd      bwd      iters      fp32 eps 1e-6: fwd      bwd      iters
+#   n1_one_inequality         10    7.1e-10  1.1e-12  17 / 3.0               4.2e-07  8.9e-07   9 / 1.8
+#   n3_box                     3    1.7e-09  3.2e-09  40 / 25.9              1.4e-06  2.5e-06  25 / 16.4
+#   n4_ball_quadratic_only     3    1.2e-09  2.9e-09  28 / 14.6              1.3e-06  3.6e-06  19 / 9.3
+#   n3_one_soc_only            3    2.2e-10  5.5e-10  15 / 6.4               7.2e-07  2.0e-06   6 / 2.8
+#   k8_n5_ragged_equalities    3    5.9e-09  3.0e-08  82 / 49.0              5.3e-06  2.0e-05  49 / 29.2
+#   n16_four_quadratics       10    3.2e-08  1.1e-07  280 / 219              2.9e-05  9.1e-05  137 / 105
+#   n32_full                  30    1.5e-07  7.7e-07  838 / 538              1.3e-04  5.6e-04  296 / 191
+#   n33_padding_lanes         10    2.2e-08  7.9e-08  182 / 89               2.0e-05  7.4e-05  83 / 42
+#   n64_c3_shape              30    1.7e-07  1.0e-06  1015 / 586             1.7e-04  1.1e-03  332 / 185
+# (the first five rows were measured with every row at the full amplitude, before the per-row depth u was added; the
+# last at amp 0.05, where 9 of its 257 rows are kink rows: amp 0.02 leaves 4)
+
+
+@functools.lru_cache(maxsize=None)
+def module_for(name):
+    from rayen_amd import projection
+    return projection.ProjectionModule(make_cs(name), create_map=False)
+
+
+def shape_of(name):
+    prog = module_for(name).program
+    return prog.n, prog.m, len(prog.soc_rows)
+
+
+def case_served(name, dtype_name):
+    shape = SHAPE[name] if name in SHAPE else shape_of(name)
+    return served(*shape, 4 if dtype_name == "float32" else 8)
+
+
+Run = namedtuple("Run", "z grad_q iters")
+
+
+@functools.lru_cache(maxsize=None)
+def mirror_run(name, dtype_name, max_iters=MAX_ITERS, eps=None):
+    """The host mirror on the seeded batch at ``dtype_name``: ``z``, ``grad_q`` for the seeded ``gy``, ``iters``."""
+    import torch
+    from rayen_amd import projection
+    dtype = getattr(torch, dtype_name)
+    cs, module = make_cs(name), module_for(name)
+    q, gy = make_inputs(name)
+    c = module.constants(dtype, torch.device("cpu"))
+    eps = EPS[dtype_name] if eps is None else eps
+    z, iters, vstar = projection.mirror_forward(c, torch.from_numpy(q).to(dtype), max_iters, eps)
+    g = torch.from_numpy(gy @ cs.NA_E).to(dtype)
+    grad = projection.mirror_backward(c, g, vstar, iters, max_iters, eps)
+    return Run(z.double().numpy(), grad.double().numpy(), iters.numpy())
+
+
+@functools.lru_cache(maxsize=None)
+def bars(name, dtype_name, capped=True):
+    """``(forward bar, backward bar, violation bar)`` of ``row_gap`` for a kernel of ``dtype_name``: KINK_FACTOR times the
+    gap of the host mirror AT THAT PRECISION against the fp64 reference on the same inputs (never the kernel's own gap);
+    in fp64 no looser than FP64_CAP (``capped=False``: without that cap, for the mirror's own run, whose fp64 backward gap
+    on n64_c3_shape is 1.1e-6 -- a shape the fp64 kernel does not stage).  The violation bar is KINK_FACTOR times the mirror's worst output residual."""
+    ref, run = reference(name), mirror_run(name, dtype_name)
+    ok = ~ref.kink
+    fwd = KINK_FACTOR * float(row_gap(run.z, ref.z).max())
+    bwd = KINK_FACTOR * float(row_gap(run.grad_q, ref.grad_q)[ok].max())
+    cs = make_cs(name)
+    viol = KINK_FACTOR * max(float(np.max(cs.getViolationRows(run.z @ cs.NA_E.T + cs.yp.T))), 0.0)
+    tiny = 64 * np.finfo(np.float32 if dtype_name == "float32" else np.float64).eps
+    if dtype_name == "float64" and capped:
+        fwd, bwd = min(fwd, FP64_CAP), min(bwd, FP64_CAP)
+    return max(fwd, tiny), max(bwd, tiny), max(viol, tiny)
+
+
+def compare(name, dtype_name, z, grad_q, iters, rows=None, capped=True):
+    """The comparisons every implementation faces (the GPU kernels in tests/test_gpu_proj.py, defective mirrors in
+    tests/test_proj_reference_host.py): returns a list of failures (empty: passed).  ``rows``: the leading rows given."""
+    ref, cs = reference(name), make_cs(name)
+    B = len(z) if rows is None else rows
+    fwd_bar, bwd_bar, viol_bar = bars(name, dtype_name, capped)
+    z, grad_q, iters = np.asarray(z, dtype=np.float64), np.asarray(grad_q, dtype=np.float64), np.asarray(iters)
+    fails = []
+    gap = row_gap(z, ref.z[:B])
+    if not np.all(gap <= fwd_bar):
+        fails.append(f"forward: worst row gap {np.nanmax(gap):.3e} > {fwd_bar:.3e} (row {int(np.nanargmax(gap))})")
+    if not np.all(np.isfinite(z)):
+        fails.append("forward: non-finite output")
+    ok = ~ref.kink[:B]
+    if np.count_nonzero(~ok) > kink_cap(B):
+        fails.append(f"{np.count_nonzero(~ok)} kink rows of {B}: over the cap {kink_cap(B)}")
+    ggap = row_gap(grad_q, ref.grad_q[:B])[ok]
+    if ggap.size and not np.all(ggap <= bwd_bar):
+        fails.append(f"backward: worst row gap {np.nanmax(ggap):.3e} > {bwd_bar:.3e}")
+    inside = ref.interior[:B]
+    if not np.all(iters[inside] == 0):
+        fails.append("an interior row took iterations")
+    if not np.array_equal(z[inside], ref.q[:B][inside]):
+        fails.append("an interior row moved")
+    if np.any(iters[~inside] == 0):
+        fails.append("a row outside the set took no iteration")
+    viol = float(np.max(cs.getViolationRows(z @ cs.NA_E.T + cs.yp.T)))
+    if not viol <= viol_bar:
+        fails.append(f"violation {viol:.3e} > {viol_bar:.3e}")
+    return fails
