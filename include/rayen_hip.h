@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 11
+#define RAYEN_ABI_VERSION 12
 
 enum {
   RAYEN_OK = 0,
@@ -440,6 +440,41 @@ int rayen_proj_backward_f32(const RayenProjPack* pack, const float* g, int64_t B
 int rayen_proj_backward_f64(const RayenProjPack* pack, const double* g, int64_t B, int64_t ldg, const double* vstar,
                             const int32_t* iters, double* grad_q, int64_t ldgq, double eps, int32_t max_iters, void* ws,
                             int64_t ws_bytes, void* stream);
+
+/* ---- Soft cost and violation of a batch (ABI v12): the reference's training loss of UU / UP / DC3
+ * (examples/cost_computer.py:69-110) and the residual metric every method is judged by, loss AND gradient in one launch
+ *
+ * Per sample y [k], over the ORIGINAL constraints (no subspace): the inequality values g, in the stacked order
+ *     lin_ineq  A1 y - b1 (m1 rows) | quad  0.5 y'P_i y + q_i'y + r_i (nq) | soc  ||M_j y + s_j|| - c_j'y - d_j (nsoc)
+ * followed by the equality rows e = A2 y - b2 (m2), give
+ *     cost  = sum relu(g)^2 + sum e^2
+ *     worst = the largest of the g and the |e|,  which = its index in that order (the lowest one among equal values)
+ *     grad  = d cost / d y = sum 2 relu(g) a + 2 relu(g) (P y + q) + 2 relu(g) (M'(My + s)/||My + s|| - c) + 2 A2'e
+ * with the cone's norm term taken as 0 where ||My + s|| == 0 and P read as its symmetric part.  A sample inside the set
+ * gets cost = 0 and a zero gradient, exactly.  A sample with a NaN gets cost = worst = NaN, which = -1 and NaN gradients;
+ * no other sample is touched.
+ *
+ * A RayenCostPack holds an fp32 and an fp64 device image of the stacked rows (all inputs fp64, row-major, read at creation:
+ * P [nq, k, k], q [nq, k], r [nq], M [sum soc_rows, k], s [sum soc_rows], c [nsoc, k], d [nsoc]); immutable afterwards.  The
+ * kernels keep the image in LDS: k <= 64; fp32 (matrix-core tiles of 32 rows x 64 columns) 8 448 bytes per tile -- a tile per
+ * 32 linear or equality rows, two per quadratic, one or two per cone (a cone of at most 64 rows) -- plus 256 per quadratic and
+ * cone, within 160 KiB; fp64 (a lane per sample) 8 (K + 1) bytes per row, K = k rounded up to 8, 16, 32 or 64, within 160
+ * KiB.  rayen_cost_served(pack, f64) says whether the precision is served; a call that is not returns
+ * RAYEN_E_UNSUPPORTED (the pack is still created).
+ *
+ * y [B, ld] (first k columns read), cost / worst / which [B] (any may be NULL), grad [B, ld_grad] (first k columns written)
+ * or NULL for the values alone.  Any B >= 0; asynchronous on the stream, no allocation, graph-capturable. */
+typedef struct RayenCostPack RayenCostPack;
+int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const double* P, const double* q, const double* r,
+                           int32_t nq, const double* M, const double* s, const double* c, const double* d,
+                           const int32_t* soc_rows, int32_t nsoc, const double* A2, const double* b2, int32_t m2, int32_t k,
+                           RayenCostPack** out);
+void rayen_cost_pack_destroy(RayenCostPack* pack);
+int rayen_cost_served(const RayenCostPack* pack, int32_t f64);
+int rayen_soft_cost_f32(const RayenCostPack* pack, const float* y, int64_t B, int64_t ld, float* cost, float* worst,
+                        int32_t* which, float* grad, int64_t ld_grad, void* stream);
+int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, int64_t ld, double* cost, double* worst,
+                        int32_t* which, double* grad, int64_t ld_grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,8 +28,14 @@ def _quad(y, P, q, r):
 
 
 class CostComputer(nn.Module):
-    def __init__(self, cs):
+    def __init__(self, cs, fused=False):
+        """``fused=True``: ``getSumSoftCostAllSamples`` is ``rayen_amd.soft_cost.SoftCost`` summed -- on a HIP device loss and
+        gradient in one launch of ``rayen_cost.hip`` -- instead of the chain of torch ops below; everything else is unchanged."""
         super().__init__()
+        self.fused = bool(fused)
+        if self.fused:
+            from .soft_cost import SoftCost
+            self.soft_cost = SoftCost(cs)
         if cs.has_quadratic_constraints:
             all_P, all_q, all_r = utils.getAllPqrFromQcs(cs.qcs)
             self.register_buffer("all_P", torch.Tensor(np.array(all_P)))
@@ -80,6 +86,8 @@ class CostComputer(nn.Module):
         return torch.cat(parts, dim=1)
 
     def getSumSoftCostAllSamples(self, y):
+        if self.fused:
+            return torch.sum(self.soft_cost(y))
         soft_cost = torch.sum(torch.square(torch.relu(self.getInequalityValues(y))))
         if self.has_linear_eq_constraints:
             soft_cost = soft_cost + torch.sum(torch.square(y[:, :, 0] @ self.A2.T - self.b2[:, 0]))

@@ -819,3 +819,101 @@ def _proj_backward(ctx, grad_z, grad_iters, grad_vstar):
 
 
 euclid_project.register_autograd(_proj_backward, setup_context=_proj_setup_context)
+
+
+# ------------------------------------------------------------------------------------------------
+# soft cost and violation (examples/cost_computer.py:69-110, ConvexConstraints.getResiduals): loss + gradient on rayen_cost.hip
+# ------------------------------------------------------------------------------------------------
+
+class CostPack:
+    """Owner of one ``RayenCostPack*``: fp32 and fp64 images of a set's stacked rows (``soft_cost.set_arrays``) on one
+    device.  Immutable, so a captured graph may keep using it."""
+
+    def __init__(self, arrays, device_index):
+        a = arrays
+        self.k = int(a["k"])
+        self.device_index = int(device_index)
+        handle = ctypes.c_void_p()
+        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
+        with torch.cuda.device(self.device_index):
+            _lib.check(_lib.load().rayen_cost_pack_create(
+                ptr(a["A1"]), ptr(a["b1"]), int(a["b1"].size), ptr(a["P"]), ptr(a["q"]), ptr(a["r"]), int(a["r"].size),
+                ptr(a["M"]), ptr(a["s"]), ptr(a["c"]), ptr(a["d"]), ptr(a["soc_rows"]), int(a["soc_rows"].size),
+                ptr(a["A2"]), ptr(a["b2"]), int(a["b2"].size), self.k, ctypes.byref(handle)), "rayen_cost_pack_create")
+        self.handle = handle
+
+    def served(self, dtype):
+        return bool(_lib.load().rayen_cost_served(self.handle, int(dtype == torch.float64)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.load().rayen_cost_pack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def soft_cost_raw(y, pack, want_grad):
+    """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``:
+    one launch."""
+    if not y.is_cuda:
+        raise RuntimeError(f"rayen_amd: the soft-cost HIP op runs on an MI355X (HIP) device only; got a {y.device} tensor")
+    if y.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"rayen_amd: unsupported dtype {y.dtype} (float32 and float64 only)")
+    if y.dim() != 2 or y.shape[1] < pack.k:
+        raise RuntimeError(f"rayen_amd: expected y of shape [B, >= {pack.k}], got {tuple(y.shape)}")
+    if y.device.index != pack.device_index:
+        raise RuntimeError("rayen_amd: input and cost pack live on different devices")
+    y = _dense_rows(y, pack.k)
+    B = y.shape[0]
+    cost = torch.empty((B,), dtype=y.dtype, device=y.device)
+    worst = torch.empty((B,), dtype=y.dtype, device=y.device)
+    which = torch.empty((B,), dtype=torch.int32, device=y.device)
+    grad = torch.empty((B, pack.k), dtype=y.dtype, device=y.device) if want_grad else None
+    with _on_device(y.device):
+        code = _entry("rayen_soft_cost_f32" if y.dtype == torch.float32 else "rayen_soft_cost_f64")(
+            pack.handle, _ptr(y), B, y.stride(0) if B else pack.k, _ptr(cost), _ptr(worst), _ptr(which), _ptr(grad),
+            pack.k, _stream(y.device.index))
+    _lib.check(code, "rayen_soft_cost")
+    return cost, worst, which, grad
+
+
+@torch.library.custom_op("rayen_amd::soft_cost", mutates_args=())
+def soft_cost(y: torch.Tensor, pack_id: int, need_grad: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(cost [B], worst [B], which [B] int32, grad [B, k])``; ``grad`` (``d cost[b] / d y[b]``, computed by the same
+    launch) is empty (``[0, k]``) unless ``need_grad``."""
+    pack = _pack(pack_id)
+    cost, worst, which, grad = soft_cost_raw(y, pack, need_grad)
+    return cost, worst, which, (grad if grad is not None else y.new_empty((0, pack.k)))
+
+
+@soft_cost.register_fake
+def _(y, pack_id, need_grad):
+    B, k = y.shape[0], _pack(pack_id).k
+    return (y.new_empty((B,)), y.new_empty((B,)), y.new_empty((B,), dtype=torch.int32),
+            y.new_empty((B if need_grad else 0, k)))
+
+
+def _cost_setup_context(ctx, inputs, output):
+    y, _, need_grad = inputs
+    ctx.width, ctx.have_grad = y.shape[1], bool(need_grad)
+    ctx.save_for_backward(output[3])
+
+
+def _cost_backward(ctx, grad_cost, grad_worst, grad_which, grad_grad):
+    (grad,) = ctx.saved_tensors
+    if grad_cost is None:
+        return None, None, None
+    if not ctx.have_grad:
+        raise RuntimeError("rayen_amd::soft_cost was called with need_grad=False; its gradient was not computed")
+    out = grad_cost.to(grad.dtype)[:, None] * grad
+    if ctx.width > grad.shape[1]:          # columns of y beyond k are not read
+        out = torch.nn.functional.pad(out, (0, ctx.width - grad.shape[1]))
+    return out, None, None
+
+
+soft_cost.register_autograd(_cost_backward, setup_context=_cost_setup_context)
