@@ -231,3 +231,71 @@ def residuals_device(raw, y):
         norms = t(np.array([np.linalg.norm(Fi, 2) for Fi in raw["F"][:-1]]))
         rel.append(-lam / (ay @ norms + float(np.linalg.norm(raw["F"][-1], 2))))
     return res, torch.stack(rel, dim=1).amax(dim=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# soft cost (tests/test_gpu_soft_cost.py, tests/test_gpu_soft_cost_sweep.py): a case has ``arrays`` (the set_arrays dict),
+# ``y [B, k]`` fp64, ``pad`` (row stride - k), ``kind`` and ``ref`` (cost_reference.reference(arrays, y))
+# ------------------------------------------------------------------------------------------------------------------
+
+COST_U = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}
+COST_RATIOS = {}        # (family, dtype_name) -> the largest gap/bar cost_check has seen for it (a report, not a bar)
+
+
+def cost_device_y(c, dtype_name):
+    """The case's rows on the device; a case with a row stride above k gets a strided view of a wider buffer of NaNs (a
+    kernel that reads or writes a column >= k shows)."""
+    import torch
+    k = int(c.arrays["k"])
+    y = torch.from_numpy(c.y.copy()).to(getattr(torch, dtype_name)).cuda()
+    if c.pad:
+        wide = torch.full((y.shape[0], y.shape[1] + c.pad), float("nan"), dtype=y.dtype, device="cuda")
+        wide[:, :y.shape[1]] = y
+        y = wide[:, :k]
+        assert y.stride(0) == k + c.pad
+    return y
+
+
+def cost_check(c, dtype_name, cost, worst, which, grad, what, family=None):
+    """(cost, worst, which, grad | None) of a kernel or of the mirror, tensors or arrays, against the fp64 reference at the
+    bars of tests/cost_reference.py.  Returns the reference the figures were held to."""
+    import cost_reference
+    ref, u = c.ref, COST_U[dtype_name]
+    # the inputs themselves are rounded to the working precision: re-reference on what the kernel read
+    yq = c.y.astype(np.float32).astype(np.float64) if dtype_name == "float32" else c.y
+    ref = cost_reference.reference(c.arrays, yq) if dtype_name == "float32" else ref
+    dvals, dcost, dgrad = cost_reference.bounds(ref, u)
+    bad = np.isnan(ref["cost"])
+    ok = ~bad
+    host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)          # noqa: E731
+    cost, worst, which = (host(t) for t in (cost, worst, which))
+    cost, worst = cost.astype(np.float64), worst.astype(np.float64)
+    assert np.array_equal(np.isnan(cost), bad) and np.array_equal(np.isnan(worst), bad), what
+    assert np.all(which[bad] == -1), what
+    rows = np.arange(len(cost))
+    wbar = dvals[rows, np.where(bad, 0, ref["which"])]
+    # the kernel's worst is the maximum of values each within its bar: it is within the largest bar of the reference's
+    wtol = np.max(dvals, axis=1)
+    ratios = [np.max((np.abs(worst - ref["worst"]) / np.maximum(wtol, 1e-300))[ok], initial=0.0),
+              np.max((np.abs(cost - ref["cost"]) / np.maximum(dcost, 1e-300))[ok], initial=0.0)]
+    print(f"{what}: worst gap/bar {ratios[0]:.3f} cost gap/bar {ratios[1]:.3f}")
+    assert np.all(np.abs(worst - ref["worst"])[ok] <= wtol[ok]), what
+    assert np.all(wbar[ok] <= wtol[ok])
+    assert np.all(np.abs(cost - ref["cost"])[ok] <= dcost[ok]), what
+    decided = cost_reference.which_is_decided(ref, dvals)
+    assert np.array_equal(which[decided], ref["which"][decided]), what
+    assert np.all((which[ok] >= 0) & (which[ok] < ref["vals"].shape[1])), what
+    if grad is not None:
+        g = host(grad).astype(np.float64)
+        ratios.append(np.max((np.abs(g - ref["grad"]) / np.maximum(dgrad, 1e-300))[ok], initial=0.0))
+        print(f"{what}: grad gap/bar {ratios[2]:.3f}")
+        assert np.all(np.abs(g - ref["grad"])[ok] <= dgrad[ok]), what
+        assert np.all(np.isnan(g[bad])), what
+    if c.kind == "inside":
+        assert np.all(cost == 0) and np.all(worst < 0), what
+        if grad is not None:
+            assert not np.any(host(grad)), what
+    if family is not None:
+        key = (family, dtype_name)
+        COST_RATIOS[key] = max(COST_RATIOS.get(key, 0.0), float(max(ratios)))
+    return ref

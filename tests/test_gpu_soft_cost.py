@@ -16,13 +16,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cost_cases                                             # noqa: E402
 import cost_reference                                         # noqa: E402
+from helpers import COST_U as U                               # noqa: E402
+from helpers import cost_check as _check                      # noqa: E402
+from helpers import cost_device_y as _device_y                # noqa: E402
 from rayen_amd import _lib, ops                               # noqa: E402
 from rayen_amd.cost_computer import CostComputer              # noqa: E402
 from rayen_amd.soft_cost import SoftCost                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DTYPES = ["float32", "float64"]
-U = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}
 _PACKS = {}
 
 
@@ -35,54 +37,6 @@ def _pack(c):
 
 def _served(c, dtype_name):
     return _pack(c).served(getattr(torch, dtype_name))
-
-
-def _device_y(c, dtype_name):
-    """The case's rows on the device; a case with a row stride above k gets a strided view of a wider buffer of NaNs (a
-    kernel that reads or writes a column >= k shows)."""
-    y = torch.from_numpy(c.y.copy()).to(getattr(torch, dtype_name)).cuda()
-    if c.pad:
-        wide = torch.full((y.shape[0], y.shape[1] + c.pad), float("nan"), dtype=y.dtype, device="cuda")
-        wide[:, :y.shape[1]] = y
-        y = wide[:, :c.cs.k]
-        assert y.stride(0) == c.cs.k + c.pad
-    return y
-
-
-def _check(c, dtype_name, cost, worst, which, grad, what):
-    ref, u = c.ref, U[dtype_name]
-    # the inputs themselves are rounded to the working precision: re-reference on what the kernel read
-    yq = c.y.astype(np.float32).astype(np.float64) if dtype_name == "float32" else c.y
-    ref = cost_reference.reference(c.arrays, yq) if dtype_name == "float32" else ref
-    dvals, dcost, dgrad = cost_reference.bounds(ref, u)
-    bad = np.isnan(ref["cost"])
-    ok = ~bad
-    cost, worst, which = (t.detach().cpu().numpy() for t in (cost, worst, which))
-    cost, worst = cost.astype(np.float64), worst.astype(np.float64)
-    assert np.array_equal(np.isnan(cost), bad) and np.array_equal(np.isnan(worst), bad), what
-    assert np.all(which[bad] == -1), what
-    rows = np.arange(len(cost))
-    wbar = dvals[rows, np.where(bad, 0, ref["which"])]
-    # the kernel's worst is the maximum of values each within its bar: it is within the largest bar of the reference's
-    wtol = np.max(dvals, axis=1)
-    print(f"{what}: worst gap/bar {np.max((np.abs(worst - ref['worst']) / wtol)[ok]):.3f} "
-          f"cost gap/bar {np.max((np.abs(cost - ref['cost']) / np.maximum(dcost, 1e-300))[ok]):.3f}")
-    assert np.all(np.abs(worst - ref["worst"])[ok] <= wtol[ok]), what
-    assert np.all(wbar[ok] <= wtol[ok])
-    assert np.all(np.abs(cost - ref["cost"])[ok] <= dcost[ok]), what
-    decided = cost_reference.which_is_decided(ref, dvals)
-    assert np.array_equal(which[decided], ref["which"][decided]), what
-    assert np.all((which[ok] >= 0) & (which[ok] < ref["vals"].shape[1])), what
-    if grad is not None:
-        g = grad.detach().cpu().numpy().astype(np.float64)
-        print(f"{what}: grad gap/bar {np.max((np.abs(g - ref['grad']) / np.maximum(dgrad, 1e-300))[ok]):.3f}")
-        assert np.all(np.abs(g - ref["grad"])[ok] <= dgrad[ok]), what
-        assert np.all(np.isnan(g[bad])), what
-    if c.kind == "inside":
-        assert np.all(cost == 0) and np.all(worst < 0), what
-        if grad is not None:
-            assert not np.any(grad.detach().cpu().numpy()), what
-    return ref
 
 
 SERVED_NOTE = "the image of this set is over the LDS limit at this precision: covered by test_refused_set_warns_once_and_matches_the_mirror"
