@@ -21,11 +21,10 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "rayen_hip.h"
+#include "rayen_side_pack.h"
 
 struct RayenBarPack {
   int device = -1, k = 0, nv = 0, nr = 0, K = 0, cus = 0;
@@ -36,7 +35,8 @@ struct RayenBarPack {
 namespace {
 
 constexpr int kThreads = 512;
-constexpr size_t kLdsBudget = 160 * 1024;     // gfx950 LDS per CU; the kernels stage nothing else
+constexpr int kMinK = 4, kMaxK = 64;          // the kernels' K: k padded to a power of two between these
+using rayen::kLdsBudget;                      // the kernels stage nothing but the image
 
 __device__ __forceinline__ float exp_(float x) { return expf(x); }
 __device__ __forceinline__ double exp_(double x) { return exp(x); }
@@ -275,11 +275,9 @@ template <> const double* image<double>(const RayenBarPack* p) { return p->img64
 template <typename T>
 size_t lds_bytes(const RayenBarPack* p) { return (size_t)(((p->nv + p->nr + 3) & ~3) + 1) * p->K * sizeof(T); }
 
-int check_device(const RayenBarPack* p) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;
-  return dev == p->device ? RAYEN_OK : RAYEN_E_DEVICE_MISMATCH;
-}
+// a leading dimension in 4-byte words: what rayen::rows_aligned16 counts in
+template <typename T>
+int64_t ld_words(int64_t ld) { return ld * (int64_t)(sizeof(T) / 4); }
 
 // workgroups: enough to cover the batch, at most as many as fit on the chip at once (LDS and waves per CU)
 unsigned grid_for(const RayenBarPack* p, int64_t B, int lgL, size_t lds) {
@@ -303,12 +301,9 @@ int launch_forward(const RayenBarPack* p, const T* q, int64_t B, int64_t ldq, T*
                    int32_t* nan_flag, hipStream_t stream) {
   const size_t lds = lds_bytes<T>(p);
   auto kern = bar_forward_kernel<T, K>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return RAYEN_E_LAUNCH;
+  if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const int m = p->nv + p->nr, lgL = group_log2(m);
-  const int vec = (reinterpret_cast<uintptr_t>(q) % 16 == 0) && ((ldq * (int64_t)sizeof(T)) % 16 == 0);
+  const int vec = rayen::rows_aligned16(q, ld_words<T>(ldq));
   const int64_t chunk = rows_per_launch(ldq > ldy ? ldq : ldy, sizeof(T));
   for (int64_t r0 = 0; r0 < B; r0 += chunk) {
     const int64_t b = B - r0 < chunk ? B - r0 : chunk;
@@ -324,14 +319,10 @@ int launch_backward(const RayenBarPack* p, const T* q, int64_t ldq, const T* row
                     T* grad_q, hipStream_t stream) {
   const size_t lds = lds_bytes<T>(p);
   auto kern = bar_backward_kernel<T, K>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return RAYEN_E_LAUNCH;
+  if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const int m = p->nv + p->nr, lgL = group_log2(m);
-  const bool ld_ok = (ldq * (int64_t)sizeof(T)) % 16 == 0;
-  const int vec_in = ld_ok && reinterpret_cast<uintptr_t>(q) % 16 == 0;
-  const int vec_out = ld_ok && reinterpret_cast<uintptr_t>(grad_q) % 16 == 0;
+  const int vec_in = rayen::rows_aligned16(q, ld_words<T>(ldq));
+  const int vec_out = rayen::rows_aligned16(grad_q, ld_words<T>(ldq));
   const int64_t chunk = rows_per_launch(ldq > p->k ? ldq : p->k, sizeof(T));
   for (int64_t r0 = 0; r0 < B; r0 += chunk) {
     const int64_t b = B - r0 < chunk ? B - r0 : chunk;
@@ -350,17 +341,12 @@ int bar_forward(const RayenBarPack* p, const T* q, int64_t B, int64_t ldq, T* y,
   const int m = p->nv + p->nr;
   if (B > 0 && (q == nullptr || y == nullptr || ldq < m || ldy < p->k)) return RAYEN_E_BAD_ARG;
   if (image<T>(p) == nullptr || lds_bytes<T>(p) > kLdsBudget) return RAYEN_E_UNSUPPORTED;
-  int rc = check_device(p);
+  int rc = rayen::check_device(p->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (p->K) {
-    case 4: return launch_forward<T, 4>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
-    case 8: return launch_forward<T, 8>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
-    case 16: return launch_forward<T, 16>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
-    case 32: return launch_forward<T, 32>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
-    case 64: return launch_forward<T, 64>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
-    default: return RAYEN_E_UNSUPPORTED;
-  }
+  return rayen::dispatch_width<kMinK, kMaxK>(p->K, [&](auto K) {
+    return launch_forward<T, K()>(p, q, B, ldq, y, ldy, rowstat, nan_flag, s);
+  });
 }
 
 template <typename T>
@@ -371,17 +357,12 @@ int bar_backward(const RayenBarPack* p, const T* q, int64_t ldq, const T* rowsta
   if (B > 0 && (q == nullptr || grad_y == nullptr || grad_q == nullptr || ldq < m || (p->nv > 0 && rowstat == nullptr)))
     return RAYEN_E_BAD_ARG;
   if (image<T>(p) == nullptr || lds_bytes<T>(p) > kLdsBudget) return RAYEN_E_UNSUPPORTED;
-  int rc = check_device(p);
+  int rc = rayen::check_device(p->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (p->K) {
-    case 4: return launch_backward<T, 4>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
-    case 8: return launch_backward<T, 8>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
-    case 16: return launch_backward<T, 16>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
-    case 32: return launch_backward<T, 32>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
-    case 64: return launch_backward<T, 64>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
-    default: return RAYEN_E_UNSUPPORTED;
-  }
+  return rayen::dispatch_width<kMinK, kMaxK>(p->K, [&](auto K) {
+    return launch_backward<T, K()>(p, q, ldq, rowstat, grad_y, B, grad_q, s);
+  });
 }
 
 template <typename T>
@@ -391,10 +372,7 @@ bool upload(const double* G, const double* yp, int k, int m, int K, T** out) {
   for (int j = 0; j < m; ++j)
     for (int i = 0; i < k; ++i) h[(size_t)gen_slot(j) * K + i] = static_cast<T>(G[(size_t)i * m + j]);
   for (int i = 0; i < k; ++i) h[(size_t)mp * K + i] = static_cast<T>(yp[i]);
-  void* d = nullptr;
-  if (hipMalloc(&d, h.size() * sizeof(T)) != hipSuccess) return false;
-  *out = static_cast<T*>(d);
-  return hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+  return rayen::upload_image(h, out);
 }
 
 }  // namespace
@@ -405,20 +383,17 @@ int rayen_bar_pack_create(const double* G, const double* yp, int32_t k, int32_t 
   if (out == nullptr) return RAYEN_E_BAD_ARG;
   *out = nullptr;
   if (G == nullptr || yp == nullptr || k <= 0 || nv < 0 || nr < 0 || nv + nr <= 0) return RAYEN_E_BAD_ARG;
-  if (k > 64) return RAYEN_E_UNSUPPORTED;
-  int dev = -1;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-      std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return RAYEN_E_NO_DEVICE;
+  if (k > kMaxK) return RAYEN_E_UNSUPPORTED;
+  int dev = -1, cus = 0;
+  if (rayen::side_pack_device(&dev, &cus, 256) != RAYEN_OK) return RAYEN_E_NO_DEVICE;
   RayenBarPack* p = new (std::nothrow) RayenBarPack();
   if (p == nullptr) return RAYEN_E_ALLOC;
   p->device = dev;
   p->k = k;
   p->nv = nv;
   p->nr = nr;
-  p->K = k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;
-  p->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  p->K = rayen::padded_width<kMinK, kMaxK>(k);
+  p->cus = cus;
   const int m = nv + nr;
   if (!upload<float>(G, yp, k, m, p->K, &p->img32) || !upload<double>(G, yp, k, m, p->K, &p->img64)) {
     rayen_bar_pack_destroy(p);
@@ -430,11 +405,11 @@ int rayen_bar_pack_create(const double* G, const double* yp, int32_t k, int32_t 
 
 void rayen_bar_pack_destroy(RayenBarPack* p) {
   if (p == nullptr) return;
-  int prev = -1;
-  const bool switched = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
-  if (p->img32) (void)hipFree(p->img32);
-  if (p->img64) (void)hipFree(p->img64);
-  if (switched) (void)hipSetDevice(prev);
+  {
+    rayen::DeviceScope on_device(p->device);
+    if (p->img32) (void)hipFree(p->img32);
+    if (p->img64) (void)hipFree(p->img64);
+  }
   delete p;
 }
 

@@ -29,7 +29,7 @@
 #include <new>
 #include <vector>
 
-#include "rayen_internal.h"
+#include "rayen_side_pack.h"
 
 namespace {
 
@@ -38,7 +38,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 enum { CT_LIN = 0, CT_EQ = 1, CT_QUAD = 2, CT_SOC = 3 };
 
 constexpr int kThreads = 256;                  // four waves: one per SIMD (the image takes most of the CU's LDS)
-constexpr size_t kLdsBudget = 160 * 1024;      // gfx950 LDS per CU
+using rayen::kLdsBudget;
+constexpr int kMinK64 = 8, kMaxK64 = 64;       // the fp64 kernel's K: k padded to a power of two between these
 constexpr int kDescWords = 8;                  // per tile / item: type, nvalid | row0, id0, form, fconst, ntiles | nrows, -, -
 
 }  // namespace
@@ -46,12 +47,12 @@ constexpr int kDescWords = 8;                  // per tile / item: type, nvalid 
 struct RayenCostPack {
   int device = -1, k = 0, n_simd = 1024;
   // fp32 image (one buffer of 4-byte words): W [nt][32][64] swizzled | rowc [nt][32] | colv [nf][64] | desc [nt][8]
-  void* img32 = nullptr;
+  int32_t* img32 = nullptr;
   int nt = 0, rowc_off = 0, colv_off = 0, desc_off = 0;
   size_t bytes32 = 0;
   bool served32 = false;
   // fp64 image (8-byte words): W [R][K] | rowc [R] | colv [nf][K] | fconst [ni] | desc [ni][8] (ints)
-  void* img64 = nullptr;
+  double* img64 = nullptr;
   int K64 = 0, ni = 0, rowc64_off = 0, colv64_off = 0, fc64_off = 0, desc64_off = 0;
   size_t bytes64 = 0;
   bool served64 = false;
@@ -478,7 +479,7 @@ bool build32(const SetView& v, RayenCostPack* p, std::vector<int32_t>* words) {
 }
 
 bool build64(const SetView& v, RayenCostPack* p, std::vector<double>* words) {
-  const int K = v.k <= 8 ? 8 : v.k <= 16 ? 16 : v.k <= 32 ? 32 : 64;
+  const int K = rayen::padded_width<kMinK64, kMaxK64>(v.k);
   int msoc = 0;
   for (int j = 0; j < v.nsoc; ++j) msoc += v.soc_rows[j];
   const int R = v.m1 + v.nq * v.k + msoc + v.m2, nf = v.nq + v.nsoc;
@@ -533,38 +534,21 @@ bool build64(const SetView& v, RayenCostPack* p, std::vector<double>* words) {
   return row == R && it == ni;
 }
 
-bool upload(const void* host, const size_t bytes, void** dev) {
-  if (hipMalloc(dev, bytes) != hipSuccess) return false;
-  return hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) == hipSuccess;
-}
-
 int check_call(const RayenCostPack* p, const void* y, const int64_t B, const int64_t ld, const void* grad, const int64_t ldg) {
   if (p == nullptr || B < 0) return RAYEN_E_BAD_ARG;
   if (B > 0 && (y == nullptr || ld < p->k || (grad != nullptr && ldg < p->k))) return RAYEN_E_BAD_ARG;
   return RAYEN_OK;
 }
 
-int check_device(const RayenCostPack* p) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;
-  return dev == p->device ? RAYEN_OK : RAYEN_E_DEVICE_MISMATCH;
-}
-
-template <typename Kern>
-bool allow_lds(Kern kern, const size_t lds) {
-  return lds <= 48 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-}
-
 template <bool GRAD>
 int launch32(const RayenCostPack* p, const float* y, int64_t B, int64_t ld, float* cost, float* worst, int32_t* which,
              float* grad, int64_t ldg, hipStream_t stream) {
   auto kern = cost_mfma_kernel<GRAD>;
-  if (!allow_lds(kern, p->bytes32)) return RAYEN_E_LAUNCH;
+  if (!rayen::allow_lds(kern, p->bytes32)) return RAYEN_E_LAUNCH;
   const int64_t grid = rayen::persistent_grid(B, 32, rayen::launch_simds(p->n_simd), kThreads / 64);
   const int vec_in = (p->k % 4 == 0) && rayen::rows_aligned16(y, ld);
   const int vec_out = GRAD && (p->k % 4 == 0) && rayen::rows_aligned16(grad, ldg);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes32, stream, static_cast<const uint4*>(p->img32),
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes32, stream, reinterpret_cast<const uint4*>(p->img32),
                      (int)(p->bytes32 / 16), p->nt, p->rowc_off, p->colv_off, p->desc_off, y, B, ld, p->k, vec_in, cost,
                      worst, which, grad, ldg, vec_out);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
@@ -574,9 +558,9 @@ template <int K, bool GRAD>
 int launch64(const RayenCostPack* p, const double* y, int64_t B, int64_t ld, double* cost, double* worst, int32_t* which,
              double* grad, int64_t ldg, hipStream_t stream) {
   auto kern = cost_lane64_kernel<K, GRAD>;
-  if (!allow_lds(kern, p->bytes64)) return RAYEN_E_LAUNCH;
+  if (!rayen::allow_lds(kern, p->bytes64)) return RAYEN_E_LAUNCH;
   const int64_t grid = rayen::persistent_grid(B, kThreads, rayen::launch_simds(p->n_simd) / 4, 1);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes64, stream, static_cast<const uint4*>(p->img64),
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes64, stream, reinterpret_cast<const uint4*>(p->img64),
                      (int)(p->bytes64 / 16), p->ni, p->rowc64_off, p->colv64_off, p->fc64_off, p->desc64_off, y, B, ld,
                      p->k, cost, worst, which, grad, ldg);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
@@ -606,24 +590,20 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
     return RAYEN_E_BAD_ARG;
   for (int j = 0; j < nsoc; ++j)
     if (soc_rows[j] <= 0) return RAYEN_E_BAD_ARG;
-  int dev = -1;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-      std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return RAYEN_E_NO_DEVICE;
+  int dev = -1, cus = 0;
+  if (rayen::side_pack_device(&dev, &cus, 256) != RAYEN_OK) return RAYEN_E_NO_DEVICE;
   RayenCostPack* p = new (std::nothrow) RayenCostPack();
   if (p == nullptr) return RAYEN_E_ALLOC;
   p->device = dev;
   p->k = k;
-  p->n_simd = prop.multiProcessorCount > 0 ? prop.multiProcessorCount * 4 : 1024;
+  p->n_simd = cus * 4;
   if (k <= 64) {     // beyond: the pack exists and every call answers RAYEN_E_UNSUPPORTED
     const SetView v{A1, b1, P, q, r, M, s, c, d, A2, b2, soc_rows, m1, nq, nsoc, m2, k};
     std::vector<int32_t> w32;
     std::vector<double> w64;
     p->served32 = build32(v, p, &w32);
     p->served64 = build64(v, p, &w64);
-    if ((p->served32 && !upload(w32.data(), p->bytes32, &p->img32)) ||
-        (p->served64 && !upload(w64.data(), p->bytes64, &p->img64))) {
+    if ((p->served32 && !rayen::upload_image(w32, &p->img32)) || (p->served64 && !rayen::upload_image(w64, &p->img64))) {
       rayen_cost_pack_destroy(p);
       return RAYEN_E_ALLOC;
     }
@@ -634,11 +614,11 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
 
 void rayen_cost_pack_destroy(RayenCostPack* p) {
   if (p == nullptr) return;
-  int prev = -1;
-  const bool switched = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
-  if (p->img32) (void)hipFree(p->img32);
-  if (p->img64) (void)hipFree(p->img64);
-  if (switched) (void)hipSetDevice(prev);
+  {
+    rayen::DeviceScope on_device(p->device);
+    if (p->img32) (void)hipFree(p->img32);
+    if (p->img64) (void)hipFree(p->img64);
+  }
   delete p;
 }
 
@@ -652,7 +632,7 @@ int rayen_soft_cost_f32(const RayenCostPack* pack, const float* y, int64_t B, in
   int rc = check_call(pack, y, B, ld, grad, ld_grad);
   if (rc != RAYEN_OK) return rc;
   if (!pack->served32) return RAYEN_E_UNSUPPORTED;
-  rc = check_device(pack);
+  rc = rayen::check_device(pack->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return grad != nullptr ? launch32<true>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st)
@@ -664,16 +644,12 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
   int rc = check_call(pack, y, B, ld, grad, ld_grad);
   if (rc != RAYEN_OK) return rc;
   if (!pack->served64) return RAYEN_E_UNSUPPORTED;
-  rc = check_device(pack);
+  rc = rayen::check_device(pack->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (pack->K64) {
-    case 8: return launch64_k<8>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
-    case 16: return launch64_k<16>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
-    case 32: return launch64_k<32>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
-    case 64: return launch64_k<64>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
-    default: return RAYEN_E_UNSUPPORTED;
-  }
+  return rayen::dispatch_width<kMinK64, kMaxK64>(pack->K64, [&](auto K) {
+    return launch64_k<K()>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
+  });
 }
 
 }  // extern "C"

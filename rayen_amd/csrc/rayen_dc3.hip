@@ -29,11 +29,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "rayen_hip.h"
+#include "rayen_side_pack.h"
 
 struct RayenDc3Pack {
   int device = -1, k = 0, n = 0, m = 0, nq = 0, no = 0, NP = 0;
@@ -46,9 +45,9 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 32;                    // steps per launch
-constexpr size_t kLdsBudget = 160 * 1024;     // gfx950 LDS per CU (256 bytes of it are left to the kernels' static variables:
-                                              // sh_t today; -Rpass-analysis=kernel-resource-usage prints the figure)
-constexpr size_t kViolBytes = 8;              // one slot per step, wide enough for the bits of a double
+constexpr int kMinNP = 4, kMaxNP = 64;        // the kernels' NP: n padded to a power of two between these (fp64: up to 32)
+using rayen::kLdsBudget;                      // 256 bytes of it are left to the kernels' static variables: sh_t today;
+                                              // -Rpass-analysis=kernel-resource-usage prints the figure
 
 struct Dims {
   int n, k, m, nq, no;
@@ -419,38 +418,24 @@ bool served(const RayenDc3Pack* p) {
   return image<T>(p) != nullptr && p->NP <= max_np && (size_t)dims_of(p).total * sizeof(T) <= kLdsBudget - 256;
 }
 
-int check_device(const RayenDc3Pack* p) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;
-  return dev == p->device ? RAYEN_OK : RAYEN_E_DEVICE_MISMATCH;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int n_chunks(int max_steps) { return (max_steps + kChunk - 1) / kChunk; }
 
+// the scratch buffers (rayen_side_layout.h): what rayen_dc3_workspace_bytes reports and what the launches are handed
 template <typename T>
-int64_t forward_ws_bytes(const RayenDc3Pack* p, int64_t B, int max_steps) {
-  size_t bytes = align256((size_t)(max_steps + 1) * kViolBytes);
-  if (n_chunks(max_steps) > 1) bytes += 2 * align256((size_t)2 * p->n * (size_t)B * sizeof(T));
-  return (int64_t)bytes;
+rayen::WsLayout<3> forward_ws(const RayenDc3Pack* p, int64_t B, int max_steps) {
+  return rayen::dc3_forward_ws(p->n, B, max_steps, n_chunks(max_steps), sizeof(T));
 }
 
 template <typename T>
-int64_t backward_ws_bytes(const RayenDc3Pack* p, int64_t B, int max_steps) {
-  return (int64_t)align256((size_t)max_steps * p->n * (size_t)B * sizeof(T));
+rayen::WsLayout<1> backward_ws(const RayenDc3Pack* p, int64_t B, int max_steps) {
+  return rayen::dc3_backward_ws(p->n, B, max_steps, sizeof(T));
 }
 
 template <typename T, int NP>
 int launch_forward(const RayenDc3Pack* p, FwdArgs<T> a, hipStream_t stream) {
   const size_t lds = (size_t)a.d.total * sizeof(T);
   auto kern = dc3_forward_kernel<T, NP>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess) {
-    (void)hipGetLastError();                      // (or the runtime's next caller finds this error waiting for it)
-    return RAYEN_E_LAUNCH;
-  }
+  if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const unsigned grid = (unsigned)((a.B + kThreads - 1) / kThreads);
   const int chunks = n_chunks(a.max_steps);
   for (int c = 0; c <= chunks; ++c) {
@@ -465,12 +450,7 @@ template <typename T, int NP>
 int launch_backward(const RayenDc3Pack* p, const BwdArgs<T>& a, hipStream_t stream) {
   const size_t lds = (size_t)a.d.total * sizeof(T);
   auto kern = dc3_backward_kernel<T, NP>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess) {
-    (void)hipGetLastError();                      // (or the runtime's next caller finds this error waiting for it)
-    return RAYEN_E_LAUNCH;
-  }
+  if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const unsigned grid = (unsigned)((a.B + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
@@ -484,12 +464,12 @@ int dc3_forward(const RayenDc3Pack* p, const T* q, int64_t B, int64_t ldq, T* y,
   if (B > 0 && (q == nullptr || y == nullptr || ldq < p->n || ldy < p->k)) return RAYEN_E_BAD_ARG;
   if (B > ((int64_t)1 << 31) - kThreads) return RAYEN_E_BAD_ARG;
   if (!served<T>(p)) return RAYEN_E_UNSUPPORTED;
-  if (ws == nullptr || ws_bytes < forward_ws_bytes<T>(p, B, max_steps)) return RAYEN_E_BAD_ARG;
-  int rc = check_device(p);
+  const rayen::WsLayout<3> w = forward_ws<T>(p, B, max_steps);
+  if (ws == nullptr || ws_bytes < (int64_t)w.total) return RAYEN_E_BAD_ARG;
+  int rc = rayen::check_device(p->device);
   if (rc != RAYEN_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t viol_bytes = align256((size_t)(max_steps + 1) * kViolBytes);
-  if (hipMemsetAsync(ws, 0, viol_bytes, s) != hipSuccess) return RAYEN_E_LAUNCH;
+  if (hipMemsetAsync(ws, 0, w.bytes[rayen::kDc3Viol], s) != hipSuccess) return RAYEN_E_LAUNCH;
   if (B == 0) {
     // an empty batch takes no step (the reference's maximum over nothing raises)
     return hipMemsetAsync(tstar, 0, sizeof(int32_t), s) == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
@@ -502,25 +482,15 @@ int dc3_forward(const RayenDc3Pack* p, const T* q, int64_t B, int64_t ldq, T* y,
   a.lr = (T)lr; a.momentum = (T)momentum; a.eps = (T)eps;
   a.max_steps = max_steps;
   a.chunk = 0;
-  a.viol = reinterpret_cast<typename BitsOf<T>::type*>(ws);
-  a.state0 = a.state1 = nullptr;
-  if (n_chunks(max_steps) > 1) {
-    const size_t one_state = align256((size_t)2 * p->n * (size_t)B * sizeof(T));
-    a.state0 = reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + viol_bytes);
-    a.state1 = reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + viol_bytes + one_state);
-  }
+  a.viol = w.at<typename BitsOf<T>::type>(ws, rayen::kDc3Viol);
+  a.state0 = w.at<T>(ws, rayen::kDc3State0);      // (null with a single chunk)
+  a.state1 = w.at<T>(ws, rayen::kDc3State1);
   a.tstar = tstar;
   a.nan_flag = nan_flag;
-  switch (p->NP) {
-    case 4: return launch_forward<T, 4>(p, a, s);
-    case 8: return launch_forward<T, 8>(p, a, s);
-    case 16: return launch_forward<T, 16>(p, a, s);
-    case 32: return launch_forward<T, 32>(p, a, s);
-    case 64:
-      if constexpr (sizeof(T) == 4) return launch_forward<T, 64>(p, a, s);
-      return RAYEN_E_UNSUPPORTED;
-    default: return RAYEN_E_UNSUPPORTED;
-  }
+  return rayen::dispatch_width<kMinNP, kMaxNP>(p->NP, [&](auto NP) {
+    if constexpr (sizeof(T) == 4 || NP() <= 32) return launch_forward<T, NP()>(p, a, s);
+    else return (int)RAYEN_E_UNSUPPORTED;
+  });
 }
 
 template <typename T>
@@ -532,8 +502,9 @@ int dc3_backward(const RayenDc3Pack* p, const T* q, int64_t B, int64_t ldq, cons
     return RAYEN_E_BAD_ARG;
   if (B > ((int64_t)1 << 31) - kThreads) return RAYEN_E_BAD_ARG;
   if (!served<T>(p)) return RAYEN_E_UNSUPPORTED;
-  if (B > 0 && (ws == nullptr || ws_bytes < backward_ws_bytes<T>(p, B, max_steps))) return RAYEN_E_BAD_ARG;
-  int rc = check_device(p);
+  const rayen::WsLayout<1> w = backward_ws<T>(p, B, max_steps);
+  if (B > 0 && (ws == nullptr || ws_bytes < (int64_t)w.total)) return RAYEN_E_BAD_ARG;
+  int rc = rayen::check_device(p->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   BwdArgs<T> a;
   a.img = image<T>(p);
@@ -543,18 +514,12 @@ int dc3_backward(const RayenDc3Pack* p, const T* q, int64_t B, int64_t ldq, cons
   a.lr = (T)lr; a.momentum = (T)momentum;
   a.max_steps = max_steps;
   a.tstar = tstar;
-  a.traj = static_cast<T*>(ws);
+  a.traj = w.at<T>(ws, 0);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (p->NP) {
-    case 4: return launch_backward<T, 4>(p, a, s);
-    case 8: return launch_backward<T, 8>(p, a, s);
-    case 16: return launch_backward<T, 16>(p, a, s);
-    case 32: return launch_backward<T, 32>(p, a, s);
-    case 64:
-      if constexpr (sizeof(T) == 4) return launch_backward<T, 64>(p, a, s);
-      return RAYEN_E_UNSUPPORTED;
-    default: return RAYEN_E_UNSUPPORTED;
-  }
+  return rayen::dispatch_width<kMinNP, kMaxNP>(p->NP, [&](auto NP) {
+    if constexpr (sizeof(T) == 4 || NP() <= 32) return launch_backward<T, NP()>(p, a, s);
+    else return (int)RAYEN_E_UNSUPPORTED;
+  });
 }
 
 template <typename T>
@@ -579,10 +544,7 @@ bool upload(const RayenDc3Pack* p, const double* A1e, const double* b1e, const d
     for (int j = 0; j < n; ++j) h[(size_t)d.off_C + (size_t)o * NP + j] = static_cast<T>(C[(size_t)o * n + j]);
     h[(size_t)d.off_c0 + o] = static_cast<T>(c0[o]);
   }
-  void* dev = nullptr;
-  if (hipMalloc(&dev, h.size() * sizeof(T)) != hipSuccess) return false;
-  *out = static_cast<T*>(dev);
-  return hipMemcpy(dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+  return rayen::upload_image(h, out);
 }
 
 }  // namespace
@@ -603,23 +565,19 @@ int rayen_dc3_pack_create(const double* A1e, const double* b1e, int32_t m, const
   for (int o = 0; o < k - n; ++o)
     if (other[o] < 0 || other[o] >= k) return RAYEN_E_BAD_ARG;
   int dev = -1;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-      std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return RAYEN_E_NO_DEVICE;
+  if (rayen::side_pack_device(&dev) != RAYEN_OK) return RAYEN_E_NO_DEVICE;
   RayenDc3Pack* p = new (std::nothrow) RayenDc3Pack();
   if (p == nullptr) return RAYEN_E_ALLOC;
   p->device = dev;
   p->k = k; p->n = n; p->m = m; p->nq = nq; p->no = k - n;
-  p->NP = n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : n <= 64 ? 64 : 0;
+  p->NP = rayen::padded_width<kMinNP, kMaxNP>(n);
   *out = p;
   if (p->NP == 0) return RAYEN_OK;        // beyond what the kernels stage: every call answers RAYEN_E_UNSUPPORTED
   const Dims d = dims_of(p);
   std::vector<int32_t> perm((size_t)k);
   for (int j = 0; j < n; ++j) perm[j] = partial[j];
   for (int o = 0; o < k - n; ++o) perm[n + o] = other[o];
-  bool ok = hipMalloc(reinterpret_cast<void**>(&p->perm), perm.size() * sizeof(int32_t)) == hipSuccess &&
-            hipMemcpy(p->perm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+  bool ok = rayen::upload_image(perm, &p->perm);
   // an image that cannot fit LDS is not uploaded (the calls answer RAYEN_E_UNSUPPORTED)
   if (ok && (size_t)d.total * sizeof(float) <= kLdsBudget - 256) ok = upload<float>(p, A1e, b1e, Pe, qe, re, C, c0, &p->img32);
   if (ok && (size_t)d.total * sizeof(double) <= kLdsBudget - 256 && p->NP <= 32)
@@ -634,19 +592,20 @@ int rayen_dc3_pack_create(const double* A1e, const double* b1e, int32_t m, const
 
 void rayen_dc3_pack_destroy(RayenDc3Pack* p) {
   if (p == nullptr) return;
-  int prev = -1;
-  const bool switched = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
-  if (p->img32) (void)hipFree(p->img32);
-  if (p->img64) (void)hipFree(p->img64);
-  if (p->perm) (void)hipFree(p->perm);
-  if (switched) (void)hipSetDevice(prev);
+  {
+    rayen::DeviceScope on_device(p->device);
+    if (p->img32) (void)hipFree(p->img32);
+    if (p->img64) (void)hipFree(p->img64);
+    if (p->perm) (void)hipFree(p->perm);
+  }
   delete p;
 }
 
 int64_t rayen_dc3_workspace_bytes(const RayenDc3Pack* p, int64_t B, int32_t max_steps, int32_t f64, int32_t backward) {
   if (p == nullptr || B < 0 || max_steps < 1) return -1;
-  if (backward) return f64 ? backward_ws_bytes<double>(p, B, max_steps) : backward_ws_bytes<float>(p, B, max_steps);
-  return f64 ? forward_ws_bytes<double>(p, B, max_steps) : forward_ws_bytes<float>(p, B, max_steps);
+  const size_t elem = f64 ? sizeof(double) : sizeof(float);
+  if (backward) return (int64_t)rayen::dc3_backward_ws(p->n, B, max_steps, elem).total;
+  return (int64_t)rayen::dc3_forward_ws(p->n, B, max_steps, n_chunks(max_steps), elem).total;
 }
 
 int rayen_dc3_forward_f32(const RayenDc3Pack* pack, const float* q, int64_t B, int64_t ldq, float* y, int64_t ldy,

@@ -19,7 +19,8 @@ inline int64_t persistent_grid(const int64_t B, const int per_wave, const int64_
   return grid_for_groups((B + per_wave - 1) / per_wave, slots, block_waves);
 }
 inline bool base_aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-// rows of `ld` floats behind `ptr` all start on 16-byte boundaries (the kernels' vec_in / vec_out: float4 pieces of a row)
+// rows of `ld` 4-byte words behind `ptr` all start on 16-byte boundaries (the kernels' vec_in / vec_out: 16-byte pieces of
+// a row).  `ld` counts floats; rows of doubles pass twice their leading dimension (rayen_bar.hip::ld_words).
 inline bool rows_aligned16(const void* ptr, const int64_t ld) { return (ld % 4 == 0) && base_aligned16(ptr); }
 
 }  // namespace rayen

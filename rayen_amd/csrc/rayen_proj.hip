@@ -31,7 +31,7 @@
 #include <new>
 #include <vector>
 
-#include "rayen_hip.h"
+#include "rayen_side_pack.h"
 
 namespace {
 constexpr int kMaxSoc = 32;
@@ -53,7 +53,7 @@ constexpr int kChunk = 32;                    // iterations per launch
 constexpr int kMaxR = 9;                      // rows of v per lane
 constexpr int kMaxRows = 64 * kMaxR;
 constexpr int kMaxN = 64;
-constexpr size_t kLdsBudget = 160 * 1024;     // gfx950 LDS per CU; 256 bytes of it are left to static variables (sh_any)
+using rayen::kLdsBudget;                      // 256 bytes of it are left to static variables (sh_any)
 
 struct Dims {
   int n, m, m_lin, n_soc, mpad;
@@ -399,31 +399,11 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
   }
 }
 
-int check_device(const RayenProjPack* p) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return RAYEN_E_NO_DEVICE;
-  return dev == p->device ? RAYEN_OK : RAYEN_E_DEVICE_MISMATCH;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <typename T>
-int64_t ws_bytes_of(const RayenProjPack* p, int64_t B, bool backward) {
-  size_t bytes = align256((size_t)B * p->n * sizeof(T)) + align256((size_t)B * sizeof(int32_t));
-  if (backward) bytes += align256((size_t)B * p->m * sizeof(T));
-  return (int64_t)bytes;
-}
-
 template <typename T, int R, bool BWD>
 int launch(const RayenProjPack* p, ProjArgs<T> a, hipStream_t stream) {
   const size_t lds = lds_bytes(a.d, sizeof(T));
   auto kern = proj_kernel<T, R, BWD>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess) {
-    (void)hipGetLastError();
-    return RAYEN_E_LAUNCH;
-  }
+  if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const int64_t groups = (a.B + kWaves - 1) / kWaves;
   int64_t per_cu = (int64_t)(kLdsBudget / (lds + 256));
   per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
@@ -445,8 +425,10 @@ int run(const RayenProjPack* p, const T* in, int64_t B, int64_t ld_in, T* out, i
     return RAYEN_E_BAD_ARG;
   if (B > ((int64_t)1 << 31) / kMaxRows) return RAYEN_E_BAD_ARG;
   if (!served<T>(p)) return RAYEN_E_UNSUPPORTED;
-  if (B > 0 && (ws == nullptr || ws_bytes < ws_bytes_of<T>(p, B, BWD))) return RAYEN_E_BAD_ARG;
-  int rc = check_device(p);
+  // the scratch buffer (rayen_side_layout.h): what rayen_proj_workspace_bytes reports and what the launches are handed
+  const rayen::WsLayout<3> w = rayen::proj_ws(p->n, p->m, B, BWD, sizeof(T));
+  if (B > 0 && (ws == nullptr || ws_bytes < (int64_t)w.total)) return RAYEN_E_BAD_ARG;
+  int rc = rayen::check_device(p->device);
   if (rc != RAYEN_OK || B == 0) return rc;
   ProjArgs<T> a;
   a.img = image<T>(p);
@@ -454,12 +436,9 @@ int run(const RayenProjPack* p, const T* in, int64_t B, int64_t ld_in, T* out, i
   std::memcpy(a.soc_row0, p->soc_row0, sizeof(a.soc_row0));
   std::memcpy(a.soc_rows, p->soc_rows, sizeof(a.soc_rows));
   a.in = in; a.B = B; a.ld_in = ld_in; a.out = out; a.ld_out = ld_out; a.iters = iters; a.vstar = vstar;
-  unsigned char* w = static_cast<unsigned char*>(ws);
-  a.xs = reinterpret_cast<T*>(w);
-  w += align256((size_t)B * p->n * sizeof(T));
-  a.status = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)B * sizeof(int32_t));
-  a.dvs = BWD ? reinterpret_cast<T*>(w) : nullptr;
+  a.xs = w.at<T>(ws, rayen::kProjXs);
+  a.status = w.at<int32_t>(ws, rayen::kProjStatus);
+  a.dvs = w.at<T>(ws, rayen::kProjDvs);              // (null in the forward)
   a.rho = (T)p->rho; a.sigma = (T)p->sigma; a.alpha = (T)p->alpha; a.eps = (T)eps;
   a.max_iters = max_iters;
   a.chunk = 0;
@@ -481,10 +460,7 @@ bool upload(const RayenProjPack* p, const double* G, const double* h, const doub
     for (int l = 0; l < p->n; ++l) img[(size_t)d.off_K + (size_t)j * p->n + l] = static_cast<T>(Kinv[(size_t)j * p->n + l]);
     img[(size_t)d.off_w0 + j] = static_cast<T>(w0[j]);
   }
-  void* dev = nullptr;
-  if (hipMalloc(&dev, img.size() * sizeof(T)) != hipSuccess) return false;
-  *out = static_cast<T*>(dev);
-  return hipMemcpy(dev, img.data(), img.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+  return rayen::upload_image(img, out);
 }
 
 }  // namespace
@@ -506,10 +482,7 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
   }
   if (rows != m) return RAYEN_E_BAD_ARG;
   int dev = -1;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-      std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return RAYEN_E_NO_DEVICE;
+  if (rayen::side_pack_device(&dev) != RAYEN_OK) return RAYEN_E_NO_DEVICE;
   RayenProjPack* p = new (std::nothrow) RayenProjPack();
   if (p == nullptr) return RAYEN_E_ALLOC;
   p->device = dev;
@@ -536,17 +509,17 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
 
 void rayen_proj_pack_destroy(RayenProjPack* p) {
   if (p == nullptr) return;
-  int prev = -1;
-  const bool switched = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
-  if (p->img32) (void)hipFree(p->img32);
-  if (p->img64) (void)hipFree(p->img64);
-  if (switched) (void)hipSetDevice(prev);
+  {
+    rayen::DeviceScope on_device(p->device);
+    if (p->img32) (void)hipFree(p->img32);
+    if (p->img64) (void)hipFree(p->img64);
+  }
   delete p;
 }
 
 int64_t rayen_proj_workspace_bytes(const RayenProjPack* p, int64_t B, int32_t f64, int32_t backward) {
   if (p == nullptr || B < 0) return -1;
-  return f64 ? ws_bytes_of<double>(p, B, backward != 0) : ws_bytes_of<float>(p, B, backward != 0);
+  return (int64_t)rayen::proj_ws(p->n, p->m, B, backward != 0, f64 ? sizeof(double) : sizeof(float)).total;
 }
 
 int rayen_proj_forward_f32(const RayenProjPack* pack, const float* q, int64_t B, int64_t ldq, float* z, int64_t ldz,

@@ -113,6 +113,18 @@ def _entry(name):
     return fn
 
 
+_TYPED = {}
+
+
+def _typed(name, dtype):
+    """The entry point ``<name>_f32`` or ``<name>_f64`` that serves ``dtype``: one dictionary lookup per call (the name is
+    put together, and looked up through ``_entry``, the first time only)."""
+    fn = _TYPED.get((name, dtype))
+    if fn is None:
+        fn = _TYPED[(name, dtype)] = _entry(name + ("_f32" if dtype == torch.float32 else "_f64"))
+    return fn
+
+
 _FWD = {(torch.float32, False): "rayen_ray_project_f32", (torch.float64, False): "rayen_ray_project_f64",
         (torch.float32, True): "rayen_ray_project_generic_f32",
         (torch.float64, True): "rayen_ray_project_generic_f64"}
@@ -177,8 +189,7 @@ def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old
         if Wt is not None:
             n = pack.consts.n
             prods = torch.mm(v if v.shape[1] == n else v[:, :n], Wt)         # [B, rows of W_ext]: the library GEMM
-            fn = _entry("rayen_ray_project_from_products_f32" if v.dtype == torch.float32
-                        else "rayen_ray_project_from_products_f64")
+            fn = _typed("rayen_ray_project_from_products", v.dtype)
             code = fn(pack.handle, _ptr(prods), prods.stride(0), _ptr(v), B, v.stride(0), _ptr(y),
                       y.stride(0) if y is not None else k, _ptr(kappa), _ptr(active), _ptr(pack.nan_flag),
                       _stream(v.device.index))
@@ -236,8 +247,7 @@ def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=F
             prods = torch.mm(v if v.shape[1] == n else v[:, :n], Wt)
             coeff = torch.empty_like(prods)
             gs = torch.empty((B, k), dtype=v.dtype, device=v.device) if identity else None
-            fn = _entry("rayen_ray_project_bwd_coefficients_f32" if v.dtype == torch.float32
-                        else "rayen_ray_project_bwd_coefficients_f64")
+            fn = _typed("rayen_ray_project_bwd_coefficients", v.dtype)
             code = fn(pack.handle, _ptr(prods), prods.stride(0), _ptr(v), B, v.stride(0), _ptr(kappa), _ptr(active),
                       _ptr(grad_y), grad_y.stride(0), _ptr(coeff), coeff.stride(0), _ptr(gs), _stream(v.device.index))
             _lib.check(code, "rayen_ray_project_bwd_coefficients")
@@ -420,33 +430,27 @@ ray_project_mapped.register_autograd(_mapped_backward, setup_context=_mapped_set
 
 
 # ------------------------------------------------------------------------------------------------
-# method='Bar' (rayen/constraint_module.py:479-486): y = G [softmax(q_v); |q_r|] + yp on rayen_bar.hip
+# What the side layers below (Bar, DC3, Euclidean projection, soft cost) share: each owns an opaque pack of the library
+# (rayen_<layer>_pack_create / _destroy: an fp32 and an fp64 image on one device), tests its input rows the same way and
+# calls a pair of typed entry points (``_typed`` above); two of them size a scratch buffer first.
 # ------------------------------------------------------------------------------------------------
 
-class BarPack:
-    """Owner of one ``RayenBarPack*``: fp32 and fp64 images of ``G = NA_E [V R]`` (k x (nv + nr)) and ``yp`` on one
-    device, plus the NaN flag its forward raises.  Immutable, so a captured graph may keep using it."""
+class _SidePack:
+    """Owner of one opaque pack of the library on one device.  Immutable, so a captured graph may keep using it."""
+    _layer = None             # "bar", "dc3", ...: rayen_<layer>_pack_create and rayen_<layer>_pack_destroy
+    handle = None
 
-    def __init__(self, G, yp, nv, nr, device_index):
-        import numpy as np
-        self.k, self.nv, self.nr = int(G.shape[0]), int(nv), int(nr)
+    def _create(self, device_index, *args):
         self.device_index = int(device_index)
-        G = np.ascontiguousarray(G, dtype=np.float64)
-        yp = np.ascontiguousarray(np.reshape(yp, -1), dtype=np.float64)
         handle = ctypes.c_void_p()
+        name = f"rayen_{self._layer}_pack_create"
         with torch.cuda.device(self.device_index):
-            _lib.check(_lib.load().rayen_bar_pack_create(G.ctypes.data, yp.ctypes.data, self.k, self.nv, self.nr,
-                                                         ctypes.byref(handle)), "rayen_bar_pack_create")
-            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+            _lib.check(_entry(name)(*args, ctypes.byref(handle)), name)
         self.handle = handle
 
-    @property
-    def width(self):
-        return self.nv + self.nr
-
     def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().rayen_bar_pack_destroy(self.handle)
+        if self.handle:
+            _entry(f"rayen_{self._layer}_pack_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover - interpreter shutdown order
@@ -456,28 +460,84 @@ class BarPack:
             pass
 
 
-def _bar_check(q, pack):
-    if not q.is_cuda:
-        raise RuntimeError("rayen_amd: the Bar layer's HIP op runs on an MI355X (HIP) device only; got a "
-                           f"{q.device} tensor")
-    if q.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
-    if q.dim() != 2 or q.shape[1] < pack.width:
-        raise RuntimeError(f"rayen_amd: expected q of shape [B, >= {pack.width}], got {tuple(q.shape)}")
-    if q.device.index != pack.device_index:
-        raise RuntimeError("rayen_amd: input and Bar pack live on different devices")
+# layer -> (how its op is called, how its pack is called) in the messages of _check_rows
+_LAYER_NAMES = {"bar": ("the Bar layer's HIP op", "Bar pack"), "dc3": ("the DC3 layer's HIP op", "DC3 pack"),
+                "proj": ("the projection's HIP op", "projection pack"), "cost": ("the soft-cost HIP op", "cost pack")}
+
+
+def _check_rows(t, width, pack, what, layer):
+    """``t`` (called ``what``) is a ``[B, >= width]`` fp32 / fp64 tensor on the HIP device of ``pack``, or this raises."""
+    if not t.is_cuda:
+        raise RuntimeError(f"rayen_amd: {_LAYER_NAMES[layer][0]} runs on an MI355X (HIP) device only; got a "
+                           f"{t.device} tensor")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"rayen_amd: unsupported dtype {t.dtype} (float32 and float64 only)")
+    if t.dim() != 2 or t.shape[1] < width:
+        raise RuntimeError(f"rayen_amd: expected {what} of shape [B, >= {width}], got {tuple(t.shape)}")
+    if t.device.index != pack.device_index:
+        raise RuntimeError(f"rayen_amd: input and {_LAYER_NAMES[layer][1]} live on different devices")
+
+
+def _host_ptr(x):
+    """Address of a numpy array for the library; an empty one is passed as NULL."""
+    return x.ctypes.data if x.size else None
+
+
+def _workspace(pack, t, backward, max_steps=None):
+    """``(scratch tensor, its size for the library)`` of a DC3 call (``max_steps`` given) or a projection call on the rows
+    of ``t``, as ``rayen_*_workspace_bytes`` sizes it; refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read here, at
+    call time)."""
+    B, f64 = t.shape[0], int(t.dtype == torch.float64)
+    if max_steps is not None:
+        name, limit, extra = "rayen_dc3_workspace_bytes", DC3_MAX_WORKSPACE_BYTES, 0
+        nbytes = int(_entry(name)(pack.handle, B, int(max_steps), f64, int(backward)))
+    else:
+        name, limit, extra = "rayen_proj_workspace_bytes", PROJ_MAX_WORKSPACE_BYTES, B * pack.m * t.element_size()   # (v*)
+        nbytes = int(_entry(name)(pack.handle, B, f64, int(backward)))
+    if nbytes < 0:
+        raise RuntimeError(f"rayen_amd: {name} refused its arguments")
+    if nbytes + extra > limit:
+        call = "backward" if backward else "forward"
+        if max_steps is not None:
+            raise RuntimeError(f"rayen_amd: the DC3 {call} of {B} rows x {max_steps} steps needs {nbytes} bytes of scratch, more "
+                               f"than ops.DC3_MAX_WORKSPACE_BYTES = {limit}; lower the step limit or split the batch")
+        raise RuntimeError(f"rayen_amd: the projection {call} of {B} rows x {pack.m} cone rows needs {nbytes + extra} bytes of "
+                           f"scratch, more than ops.PROJ_MAX_WORKSPACE_BYTES = {limit}; split the batch")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=t.device), nbytes
+
+
+# ------------------------------------------------------------------------------------------------
+# method='Bar' (rayen/constraint_module.py:479-486): y = G [softmax(q_v); |q_r|] + yp on rayen_bar.hip
+# ------------------------------------------------------------------------------------------------
+
+class BarPack(_SidePack):
+    """Owner of one ``RayenBarPack*``: fp32 and fp64 images of ``G = NA_E [V R]`` (k x (nv + nr)) and ``yp`` on one
+    device, plus the NaN flag its forward raises."""
+    _layer = "bar"
+
+    def __init__(self, G, yp, nv, nr, device_index):
+        import numpy as np
+        self.k, self.nv, self.nr = int(G.shape[0]), int(nv), int(nr)
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        yp = np.ascontiguousarray(np.reshape(yp, -1), dtype=np.float64)
+        self._create(device_index, G.ctypes.data, yp.ctypes.data, self.k, self.nv, self.nr)
+        self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+
+    @property
+    def width(self):
+        return self.nv + self.nr
 
 
 def bar_forward_raw(q, pack, want_rowstat=True):
     """``(y [B, k], rowstat [B] | None)`` through ``rayen_bar_forward_*``; ``rowstat`` is the per-row log-sum-exp of
     the vertex logits (the backward's input)."""
-    _bar_check(q, pack)
+    _check_rows(q, pack.width, pack, "q", "bar")
     q = _dense_rows(q, pack.width)
     B = q.shape[0]
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     rowstat = torch.empty((B,), dtype=q.dtype, device=q.device) if want_rowstat else None
     with _on_device(q.device):
-        code = _entry("rayen_bar_forward_f32" if q.dtype == torch.float32 else "rayen_bar_forward_f64")(
+        code = _typed("rayen_bar_forward", q.dtype)(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.width, _ptr(y), pack.k, _ptr(rowstat),
             _ptr(pack.nan_flag), _stream(q.device.index))
     _lib.check(code, "rayen_bar_forward")
@@ -486,14 +546,14 @@ def bar_forward_raw(q, pack, want_rowstat=True):
 
 def bar_backward_raw(q, rowstat, grad_y, pack):
     """``grad_q`` (same shape as ``q``; columns beyond ``nv + nr`` are zero) through ``rayen_bar_backward_*``."""
-    _bar_check(q, pack)
+    _check_rows(q, pack.width, pack, "q", "bar")
     q = _dense_rows(q, pack.width).contiguous()
     grad_y = grad_y.to(q.dtype).contiguous()
     rowstat = rowstat.contiguous()
     B = q.shape[0]
     grad_q = torch.empty_like(q) if q.shape[1] == pack.width else torch.zeros_like(q)
     with _on_device(q.device):
-        code = _entry("rayen_bar_backward_f32" if q.dtype == torch.float32 else "rayen_bar_backward_f64")(
+        code = _typed("rayen_bar_backward", q.dtype)(
             pack.handle, _ptr(q), q.shape[1], _ptr(rowstat), _ptr(grad_y), B, _ptr(grad_q), _stream(q.device.index))
     _lib.check(code, "rayen_bar_backward")
     return grad_q
@@ -546,64 +606,24 @@ bar_project.register_autograd(_bar_backward, setup_context=_bar_setup_context)
 DC3_MAX_WORKSPACE_BYTES = 8 << 30
 
 
-class Dc3Pack:
+class Dc3Pack(_SidePack):
     """Owner of one ``RayenDc3Pack*``: fp32 and fp64 images of the effective forms (``rayen_amd/dc3.py::pack_arrays``) on one
-    device, plus the NaN flag its forward raises.  Immutable, so a captured graph may keep using it."""
+    device, plus the NaN flag its forward raises."""
+    _layer = "dc3"
 
     def __init__(self, arrays, device_index):
-        a = arrays
+        a, ptr = arrays, _host_ptr
         self.n, self.k = int(a["n"]), int(a["k"])
         self.inequalities = int(a["A1e"].shape[0]) + int(a["Pe"].shape[0])
-        self.device_index = int(device_index)
-        handle = ctypes.c_void_p()
-        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-        with torch.cuda.device(self.device_index):
-            _lib.check(_lib.load().rayen_dc3_pack_create(
-                ptr(a["A1e"]), ptr(a["b1e"]), int(a["A1e"].shape[0]), ptr(a["Pe"]), ptr(a["qe"]), ptr(a["re"]),
-                int(a["Pe"].shape[0]), ptr(a["C"]), ptr(a["c0"]), ptr(a["partial"]), ptr(a["other"]), self.n, self.k,
-                ctypes.byref(handle)), "rayen_dc3_pack_create")
-            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
-        self.handle = handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().rayen_dc3_pack_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _dc3_check(q, pack):
-    if not q.is_cuda:
-        raise RuntimeError("rayen_amd: the DC3 layer's HIP op runs on an MI355X (HIP) device only; got a "
-                           f"{q.device} tensor")
-    if q.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
-    if q.dim() != 2 or q.shape[1] < pack.n:
-        raise RuntimeError(f"rayen_amd: expected q of shape [B, >= {pack.n}], got {tuple(q.shape)}")
-    if q.device.index != pack.device_index:
-        raise RuntimeError("rayen_amd: input and DC3 pack live on different devices")
-
-
-def _dc3_workspace(pack, q, max_steps, backward):
-    nbytes = int(_lib.load().rayen_dc3_workspace_bytes(pack.handle, q.shape[0], int(max_steps),
-                                                       int(q.dtype == torch.float64), int(backward)))
-    if nbytes < 0:
-        raise RuntimeError("rayen_amd: rayen_dc3_workspace_bytes refused its arguments")
-    if nbytes > DC3_MAX_WORKSPACE_BYTES:
-        raise RuntimeError(f"rayen_amd: the DC3 {'backward' if backward else 'forward'} of {q.shape[0]} rows x {max_steps} "
-                           f"steps needs {nbytes} bytes of scratch, more than ops.DC3_MAX_WORKSPACE_BYTES = "
-                           f"{DC3_MAX_WORKSPACE_BYTES}; lower the step limit or split the batch")
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device), nbytes
+        self._create(device_index, ptr(a["A1e"]), ptr(a["b1e"]), int(a["A1e"].shape[0]), ptr(a["Pe"]), ptr(a["qe"]),
+                     ptr(a["re"]), int(a["Pe"].shape[0]), ptr(a["C"]), ptr(a["c0"]), ptr(a["partial"]), ptr(a["other"]),
+                     self.n, self.k)
+        self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
 
 
 def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
     """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*``; ``steps`` is the batch-global number of steps."""
-    _dc3_check(q, pack)
+    _check_rows(q, pack.n, pack, "q", "dc3")
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
     if pack.inequalities == 0:
@@ -613,8 +633,8 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     steps = torch.empty((1,), dtype=torch.int32, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _dc3_workspace(pack, q, max_steps, False)
-        code = _entry("rayen_dc3_forward_f32" if q.dtype == torch.float32 else "rayen_dc3_forward_f64")(
+        ws, nbytes = _workspace(pack, q, False, max_steps)
+        code = _typed("rayen_dc3_forward", q.dtype)(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(y), pack.k, float(lr), float(momentum),
             float(eps), int(max_steps), _ptr(steps), _ptr(ws), nbytes, _ptr(pack.nan_flag), _stream(q.device.index))
     _lib.check(code, "rayen_dc3_forward")
@@ -623,15 +643,15 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
 
 def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps):
     """``grad_q`` (same shape as ``q``; columns beyond ``n`` are zero) through ``rayen_dc3_backward_*``."""
-    _dc3_check(q, pack)
+    _check_rows(q, pack.n, pack, "q", "dc3")
     q = _dense_rows(q, pack.n)
     grad_y = grad_y.to(q.dtype).contiguous()
     B = q.shape[0]
     grad_q = torch.empty((B, q.shape[1]), dtype=q.dtype, device=q.device) if q.shape[1] == pack.n else \
         torch.zeros((B, q.shape[1]), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _dc3_workspace(pack, q, max_steps, True)
-        code = _entry("rayen_dc3_backward_f32" if q.dtype == torch.float32 else "rayen_dc3_backward_f64")(
+        ws, nbytes = _workspace(pack, q, True, max_steps)
+        code = _typed("rayen_dc3_backward", q.dtype)(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(grad_y), pack.k, _ptr(grad_q),
             grad_q.stride(0) if B else pack.n, float(lr), float(momentum), int(max_steps), _ptr(steps), _ptr(ws), nbytes,
             _stream(q.device.index))
@@ -688,71 +708,28 @@ dc3_project.register_autograd(_dc3_backward, setup_context=_dc3_setup_context)
 PROJ_MAX_WORKSPACE_BYTES = 8 << 30
 
 
-class ProjPack:
-    """Owner of one ``RayenProjPack*``: fp32 and fp64 images of a ``projection.Program`` on one device.  Immutable, so a
-    captured graph may keep using it."""
+class ProjPack(_SidePack):
+    """Owner of one ``RayenProjPack*``: fp32 and fp64 images of a ``projection.Program`` on one device."""
+    _layer = "proj"
 
     def __init__(self, arrays, device_index):
-        a = arrays
+        a, ptr = arrays, _host_ptr
         self.n, self.m = int(a["n"]), int(a["m"])
-        self.device_index = int(device_index)
-        handle = ctypes.c_void_p()
-        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-        with torch.cuda.device(self.device_index):
-            _lib.check(_lib.load().rayen_proj_pack_create(
-                ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]), ptr(a["w0"]), self.n, self.m, int(a["m_lin"]),
-                ptr(a["soc_rows"]), int(a["soc_rows"].size), float(a["rho"]), float(a["sigma"]), float(a["alpha"]),
-                ctypes.byref(handle)), "rayen_proj_pack_create")
-        self.handle = handle
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().rayen_proj_pack_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _proj_check(q, pack, what="q"):
-    if not q.is_cuda:
-        raise RuntimeError("rayen_amd: the projection's HIP op runs on an MI355X (HIP) device only; got a "
-                           f"{q.device} tensor")
-    if q.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"rayen_amd: unsupported dtype {q.dtype} (float32 and float64 only)")
-    if q.dim() != 2 or q.shape[1] < pack.n:
-        raise RuntimeError(f"rayen_amd: expected {what} of shape [B, >= {pack.n}], got {tuple(q.shape)}")
-    if q.device.index != pack.device_index:
-        raise RuntimeError("rayen_amd: input and projection pack live on different devices")
-
-
-def _proj_workspace(pack, q, backward):
-    nbytes = int(_lib.load().rayen_proj_workspace_bytes(pack.handle, q.shape[0], int(q.dtype == torch.float64),
-                                                        int(backward)))
-    if nbytes < 0:
-        raise RuntimeError("rayen_amd: rayen_proj_workspace_bytes refused its arguments")
-    total = nbytes + q.shape[0] * pack.m * q.element_size()
-    if total > PROJ_MAX_WORKSPACE_BYTES:
-        raise RuntimeError(f"rayen_amd: the projection {'backward' if backward else 'forward'} of {q.shape[0]} rows x "
-                           f"{pack.m} cone rows needs {total} bytes of scratch, more than ops.PROJ_MAX_WORKSPACE_BYTES = "
-                           f"{PROJ_MAX_WORKSPACE_BYTES}; split the batch")
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device), nbytes
+        self._create(device_index, ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]), ptr(a["w0"]), self.n, self.m, int(a["m_lin"]),
+                     ptr(a["soc_rows"]), int(a["soc_rows"].size), float(a["rho"]), float(a["sigma"]), float(a["alpha"]))
 
 
 def proj_forward_raw(q, pack, max_iters, eps):
     """``(z [B, n], iters [B] int32, vstar [B, m])`` through ``rayen_proj_forward_*``."""
-    _proj_check(q, pack)
+    _check_rows(q, pack.n, pack, "q", "proj")
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
     z = torch.empty((B, pack.n), dtype=q.dtype, device=q.device)
     iters = torch.empty((B,), dtype=torch.int32, device=q.device)
     vstar = torch.empty((B, pack.m), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _proj_workspace(pack, q, False)
-        code = _entry("rayen_proj_forward_f32" if q.dtype == torch.float32 else "rayen_proj_forward_f64")(
+        ws, nbytes = _workspace(pack, q, False)
+        code = _typed("rayen_proj_forward", q.dtype)(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(z), pack.n, _ptr(iters), _ptr(vstar),
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(q.device.index))
     _lib.check(code, "rayen_proj_forward")
@@ -761,14 +738,14 @@ def proj_forward_raw(q, pack, max_iters, eps):
 
 def proj_backward_raw(grad_z, vstar, iters, pack, max_iters, eps):
     """``grad_q [B, n] = J grad_z`` row by row through ``rayen_proj_backward_*``."""
-    _proj_check(grad_z, pack, "grad_z")
+    _check_rows(grad_z, pack.n, pack, "grad_z", "proj")
     g = _dense_rows(grad_z, pack.n)
     vstar, iters = vstar.contiguous(), iters.contiguous()
     B = g.shape[0]
     grad_q = torch.empty((B, pack.n), dtype=g.dtype, device=g.device)
     with _on_device(g.device):
-        ws, nbytes = _proj_workspace(pack, g, True)
-        code = _entry("rayen_proj_backward_f32" if g.dtype == torch.float32 else "rayen_proj_backward_f64")(
+        ws, nbytes = _workspace(pack, g, True)
+        code = _typed("rayen_proj_backward", g.dtype)(
             pack.handle, _ptr(g), B, g.stride(0) if B else pack.n, _ptr(vstar), _ptr(iters), _ptr(grad_q), pack.n,
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(g.device.index))
     _lib.check(code, "rayen_proj_backward")
@@ -825,49 +802,26 @@ euclid_project.register_autograd(_proj_backward, setup_context=_proj_setup_conte
 # soft cost and violation (examples/cost_computer.py:69-110, ConvexConstraints.getResiduals): loss + gradient on rayen_cost.hip
 # ------------------------------------------------------------------------------------------------
 
-class CostPack:
+class CostPack(_SidePack):
     """Owner of one ``RayenCostPack*``: fp32 and fp64 images of a set's stacked rows (``soft_cost.set_arrays``) on one
-    device.  Immutable, so a captured graph may keep using it."""
+    device."""
+    _layer = "cost"
 
     def __init__(self, arrays, device_index):
-        a = arrays
+        a, ptr = arrays, _host_ptr
         self.k = int(a["k"])
-        self.device_index = int(device_index)
-        handle = ctypes.c_void_p()
-        ptr = lambda x: x.ctypes.data if x.size else None          # noqa: E731
-        with torch.cuda.device(self.device_index):
-            _lib.check(_lib.load().rayen_cost_pack_create(
-                ptr(a["A1"]), ptr(a["b1"]), int(a["b1"].size), ptr(a["P"]), ptr(a["q"]), ptr(a["r"]), int(a["r"].size),
-                ptr(a["M"]), ptr(a["s"]), ptr(a["c"]), ptr(a["d"]), ptr(a["soc_rows"]), int(a["soc_rows"].size),
-                ptr(a["A2"]), ptr(a["b2"]), int(a["b2"].size), self.k, ctypes.byref(handle)), "rayen_cost_pack_create")
-        self.handle = handle
+        self._create(device_index, ptr(a["A1"]), ptr(a["b1"]), int(a["b1"].size), ptr(a["P"]), ptr(a["q"]), ptr(a["r"]),
+                     int(a["r"].size), ptr(a["M"]), ptr(a["s"]), ptr(a["c"]), ptr(a["d"]), ptr(a["soc_rows"]),
+                     int(a["soc_rows"].size), ptr(a["A2"]), ptr(a["b2"]), int(a["b2"].size), self.k)
 
     def served(self, dtype):
-        return bool(_lib.load().rayen_cost_served(self.handle, int(dtype == torch.float64)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().rayen_cost_pack_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
+        return bool(_entry("rayen_cost_served")(self.handle, int(dtype == torch.float64)))
 
 
 def soft_cost_raw(y, pack, want_grad):
     """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``:
     one launch."""
-    if not y.is_cuda:
-        raise RuntimeError(f"rayen_amd: the soft-cost HIP op runs on an MI355X (HIP) device only; got a {y.device} tensor")
-    if y.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"rayen_amd: unsupported dtype {y.dtype} (float32 and float64 only)")
-    if y.dim() != 2 or y.shape[1] < pack.k:
-        raise RuntimeError(f"rayen_amd: expected y of shape [B, >= {pack.k}], got {tuple(y.shape)}")
-    if y.device.index != pack.device_index:
-        raise RuntimeError("rayen_amd: input and cost pack live on different devices")
+    _check_rows(y, pack.k, pack, "y", "cost")
     y = _dense_rows(y, pack.k)
     B = y.shape[0]
     cost = torch.empty((B,), dtype=y.dtype, device=y.device)
@@ -875,7 +829,7 @@ def soft_cost_raw(y, pack, want_grad):
     which = torch.empty((B,), dtype=torch.int32, device=y.device)
     grad = torch.empty((B, pack.k), dtype=y.dtype, device=y.device) if want_grad else None
     with _on_device(y.device):
-        code = _entry("rayen_soft_cost_f32" if y.dtype == torch.float32 else "rayen_soft_cost_f64")(
+        code = _typed("rayen_soft_cost", y.dtype)(
             pack.handle, _ptr(y), B, y.stride(0) if B else pack.k, _ptr(cost), _ptr(worst), _ptr(which), _ptr(grad),
             pack.k, _stream(y.device.index))
     _lib.check(code, "rayen_soft_cost")
