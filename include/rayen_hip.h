@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 12
+#define RAYEN_ABI_VERSION 13
 
 enum {
   RAYEN_OK = 0,
@@ -462,6 +462,22 @@ int rayen_proj_backward_f64(const RayenProjPack* pack, const double* g, int64_t 
  * KiB.  rayen_cost_served(pack, f64) says whether the precision is served; a call that is not returns
  * RAYEN_E_UNSUPPORTED (the pack is still created).
  *
+ * The set's LMI  F(y) = F_k + sum_a y_a F_a >= 0  (ABI v13) is one more value, g = -lambda_min(F(y)), between the cones and
+ * the equality rows in the stacked order (index m1 + nq + nsoc; the equality rows' indices then start one higher), with
+ *     cost += relu(g)^2,   grad_a += 2 relu(g) dg/dy_a = -2 relu(g) x'F_a x,   x the unit eigenvector of lambda_min(F(y)).
+ * rayen_cost_pack_set_lmi(pack, F, r) adds it to a pack: F [k + 1, r, r] fp64, row-major, the constant term F_k LAST, the
+ * lower triangles read; at most once per pack and before the pack's first evaluation (a second LMI, r < 1 or a null
+ * argument: RAYEN_E_BAD_ARG).  A set that is ONE LMI is a pack created with m1 = nq = nsoc = m2 = 0 (such a pack serves
+ * nothing until its LMI is set).  The LMI runs on a kernel of its own, one 64-lane wave per sample with the r x r matrix in
+ * LDS: r (r | 1) + 6 r + 3 k + 10 elements within 150 KiB -- r <= ~190 in fp32, ~135 in fp64 -- and any k that leaves room
+ * (the generators stay in global memory).  A call on a set with an LMI is ONE launch when the LMI is the set's only
+ * constraint and TWO otherwise: the rows' kernel, then the LMI's on the same stream, which adds to cost and grad and takes
+ * worst / which where g is larger (on an exact tie it wins over an equality row and loses to an inequality); such a call
+ * that asks for which must ask for worst too (RAYEN_E_BAD_ARG).  rayen_cost_served answers for the WHOLE set: the rows
+ * (k <= 64 and the limits above) and the LMI must both fit at that precision, else the call returns RAYEN_E_UNSUPPORTED
+ * before anything is launched.  A sample inside gets exactly 0 from the LMI and skips its eigenvector work; a sample whose
+ * y is not finite gets cost = worst = NaN, which = -1.
+ *
  * y [B, ld] (first k columns read), cost / worst / which [B] (any may be NULL), grad [B, ld_grad] (first k columns written)
  * or NULL for the values alone.  Any B >= 0; asynchronous on the stream, no allocation, graph-capturable. */
 typedef struct RayenCostPack RayenCostPack;
@@ -469,6 +485,7 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
                            int32_t nq, const double* M, const double* s, const double* c, const double* d,
                            const int32_t* soc_rows, int32_t nsoc, const double* A2, const double* b2, int32_t m2, int32_t k,
                            RayenCostPack** out);
+int rayen_cost_pack_set_lmi(RayenCostPack* pack, const double* F, int32_t r);
 void rayen_cost_pack_destroy(RayenCostPack* pack);
 int rayen_cost_served(const RayenCostPack* pack, int32_t f64);
 int rayen_soft_cost_f32(const RayenCostPack* pack, const float* y, int64_t B, int64_t ld, float* cost, float* worst,

@@ -10,7 +10,7 @@ import os
 
 from ._build import LIBRARY
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 SEG_LIN, SEG_QUAD_SYM, SEG_QUAD_FAC, SEG_SOC, SEG_LMI = range(5)
 E_UNSUPPORTED = -6      # RAYEN_E_UNSUPPORTED (include/rayen_hip.h)
@@ -36,7 +36,7 @@ EXPORTS = (
     "rayen_dc3_forward_f64", "rayen_dc3_backward_f32", "rayen_dc3_backward_f64",
     "rayen_proj_pack_create", "rayen_proj_pack_destroy", "rayen_proj_workspace_bytes", "rayen_proj_forward_f32",
     "rayen_proj_forward_f64", "rayen_proj_backward_f32", "rayen_proj_backward_f64",
-    "rayen_cost_pack_create", "rayen_cost_pack_destroy", "rayen_cost_served", "rayen_soft_cost_f32", "rayen_soft_cost_f64",
+    "rayen_cost_pack_create", "rayen_cost_pack_set_lmi", "rayen_cost_pack_destroy", "rayen_cost_served", "rayen_soft_cost_f32", "rayen_soft_cost_f64",
 )
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
@@ -187,6 +187,8 @@ def load():
     lib.rayen_cost_pack_create.restype = ctypes.c_int
     lib.rayen_cost_pack_create.argtypes = [p, p, i32, p, p, p, i32, p, p, p, p, p, i32, p, p, i32, i32,
                                            ctypes.POINTER(ctypes.c_void_p)]
+    lib.rayen_cost_pack_set_lmi.restype = ctypes.c_int
+    lib.rayen_cost_pack_set_lmi.argtypes = [p, p, i32]
     lib.rayen_cost_pack_destroy.restype = None
     lib.rayen_cost_pack_destroy.argtypes = [p]
     lib.rayen_cost_served.restype = ctypes.c_int

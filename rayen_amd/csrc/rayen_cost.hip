@@ -3,6 +3,8 @@
 //
 //     cost[b]  = sum_r relu(g_r(y_b))^2 + sum_r (A2 y_b - b2)_r^2        g: A1 y - b1 | 0.5 y'Py + q'y + r | ||My + s|| - c'y - d
 //     worst[b] = the largest g_r (with |A2 y - b2|_r counted),  which[b] = its index in the order lin_ineq, quad, soc, lin_eq
+//     (a set's LMI, one value between soc and lin_eq, is rayen_cost_lmi.hip's: a second launch that adds to this one's
+//     outputs; the kernels here then write the equality rows' indices one higher -- eq_shift, 0 without an LMI)
 //     grad[b]  = d cost[b] / d y_b = sum 2 relu(g) a + 2 relu(g) (P y + q) + 2 relu(g) (M'(My + s)/||My + s|| - c) + 2 A2'(A2 y - b2)
 //
 // fp32: a wave owns 32 samples.  The stacked rows W (A1 | P_i | M_j | A2, padded to tiles of 32 rows x 64 columns) are
@@ -29,6 +31,7 @@
 #include <new>
 #include <vector>
 
+#include "rayen_cost_lmi.h"
 #include "rayen_side_pack.h"
 
 namespace {
@@ -56,6 +59,10 @@ struct RayenCostPack {
   int K64 = 0, ni = 0, rowc64_off = 0, colv64_off = 0, fc64_off = 0, desc64_off = 0;
   size_t bytes64 = 0;
   bool served64 = false;
+  // the set's LMI (rayen_cost_pack_set_lmi; rayen_cost_lmi.hip).  n_rows: the rows the images above hold; lmi_id: the
+  // LMI's index in the stacked order; eq_shift: what the equality rows' indices move up by (1 with an LMI, 0 without)
+  rayen::CostLmiImage* lmi = nullptr;
+  int n_rows = 0, lmi_id = 0, eq_shift = 0;
 };
 
 namespace {
@@ -112,7 +119,8 @@ __global__ __launch_bounds__(kThreads) void cost_mfma_kernel(const uint4* __rest
                                                              const float* __restrict__ y, const int64_t B, const int64_t ld,
                                                              const int k, const int vec_in, float* __restrict__ cost,
                                                              float* __restrict__ worst, int32_t* __restrict__ which,
-                                                             float* __restrict__ grad, const int64_t ldg, const int vec_out) {
+                                                             float* __restrict__ grad, const int64_t ldg, const int vec_out,
+                                                             const int eq_shift) {
   extern __shared__ __align__(16) unsigned char cost_smem[];
   {
     uint4* dst = reinterpret_cast<uint4*>(cost_smem);
@@ -166,6 +174,7 @@ __global__ __launch_bounds__(kThreads) void cost_mfma_kernel(const uint4* __rest
       const float* __restrict__ Wt = W + (size_t)t * 2048;
       if (type == CT_LIN || type == CT_EQ) {
         f32x16 T0 = tile_product(Wt, yr, i, h);
+        const int idr = type == CT_EQ ? id0 + eq_shift : id0;     // (an LMI sits between the inequalities and these)
         bool any = false;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -176,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void cost_mfma_kernel(const uint4* __rest
           const float val = type == CT_EQ ? fabsf(g) : g;
           if (valid) {
             cost_half = fmaf(p, p, cost_half);
-            if (val > wv) { wv = val; wi = id0 + R; }
+            if (val > wv) { wv = val; wi = idr + R; }
           }
           const float cf = valid ? 2.0f * p : 0.0f;
           T0[r] = cf;
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void cost_lane64_kernel(const uint4* __re
                                                                const int64_t B, const int64_t ld, const int k,
                                                                double* __restrict__ cost, double* __restrict__ worst,
                                                                int32_t* __restrict__ which, double* __restrict__ grad,
-                                                               const int64_t ldg) {
+                                                               const int64_t ldg, const int eq_shift) {
   extern __shared__ __align__(16) unsigned char cost_smem[];
   {
     uint4* dst = reinterpret_cast<uint4*>(cost_smem);
@@ -328,13 +337,14 @@ __global__ __launch_bounds__(kThreads) void cost_lane64_kernel(const uint4* __re
       const int type = d[0], row0 = d[1], id0 = d[2], form = d[3], nrows = d[5];
       const double fconst = fc[it];
       if (type == CT_LIN || type == CT_EQ) {
+        const int idr = type == CT_EQ ? id0 + eq_shift : id0;
         for (int r = 0; r < nrows; ++r) {
           const double* __restrict__ w = W + (size_t)(row0 + r) * K;
           const double g = dot(w) - rowc[row0 + r];
           const double p = type == CT_EQ ? g : relu_(g);
           const double val = type == CT_EQ ? fabs(g) : g;
           cs = fma(p, p, cs);
-          if (val > wv) { wv = val; wi = id0 + r; }
+          if (val > wv) { wv = val; wi = idr + r; }
           if (GRAD && !(p == 0.0)) {
             const double cf = 2.0 * p;
 #pragma unroll
@@ -550,7 +560,7 @@ int launch32(const RayenCostPack* p, const float* y, int64_t B, int64_t ld, floa
   const int vec_out = GRAD && (p->k % 4 == 0) && rayen::rows_aligned16(grad, ldg);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes32, stream, reinterpret_cast<const uint4*>(p->img32),
                      (int)(p->bytes32 / 16), p->nt, p->rowc_off, p->colv_off, p->desc_off, y, B, ld, p->k, vec_in, cost,
-                     worst, which, grad, ldg, vec_out);
+                     worst, which, grad, ldg, vec_out, p->eq_shift);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 
@@ -562,7 +572,7 @@ int launch64(const RayenCostPack* p, const double* y, int64_t B, int64_t ld, dou
   const int64_t grid = rayen::persistent_grid(B, kThreads, rayen::launch_simds(p->n_simd) / 4, 1);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), p->bytes64, stream, reinterpret_cast<const uint4*>(p->img64),
                      (int)(p->bytes64 / 16), p->ni, p->rowc64_off, p->colv64_off, p->fc64_off, p->desc64_off, y, B, ld,
-                     p->k, cost, worst, which, grad, ldg);
+                     p->k, cost, worst, which, grad, ldg, p->eq_shift);
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
 
@@ -583,7 +593,7 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
                            RayenCostPack** out) {
   if (out == nullptr) return RAYEN_E_BAD_ARG;
   *out = nullptr;
-  if (k <= 0 || m1 < 0 || nq < 0 || nsoc < 0 || m2 < 0 || m1 + nq + nsoc + m2 <= 0) return RAYEN_E_BAD_ARG;
+  if (k <= 0 || m1 < 0 || nq < 0 || nsoc < 0 || m2 < 0) return RAYEN_E_BAD_ARG;     // (no rows: a set that is one LMI)
   if ((m1 > 0 && (A1 == nullptr || b1 == nullptr)) || (nq > 0 && (P == nullptr || q == nullptr || r == nullptr)) ||
       (nsoc > 0 && (M == nullptr || s == nullptr || c == nullptr || d == nullptr || soc_rows == nullptr)) ||
       (m2 > 0 && (A2 == nullptr || b2 == nullptr)))
@@ -597,7 +607,9 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
   p->device = dev;
   p->k = k;
   p->n_simd = cus * 4;
-  if (k <= 64) {     // beyond: the pack exists and every call answers RAYEN_E_UNSUPPORTED
+  p->n_rows = m1 + nq + nsoc + m2;
+  p->lmi_id = m1 + nq + nsoc;
+  if (k <= 64 && p->n_rows > 0) {     // k beyond: the pack exists and a call on its rows answers RAYEN_E_UNSUPPORTED
     const SetView v{A1, b1, P, q, r, M, s, c, d, A2, b2, soc_rows, m1, nq, nsoc, m2, k};
     std::vector<int32_t> w32;
     std::vector<double> w64;
@@ -618,37 +630,76 @@ void rayen_cost_pack_destroy(RayenCostPack* p) {
     rayen::DeviceScope on_device(p->device);
     if (p->img32) (void)hipFree(p->img32);
     if (p->img64) (void)hipFree(p->img64);
+    rayen::cost_lmi_free(p->lmi);
   }
   delete p;
 }
 
+int rayen_cost_pack_set_lmi(RayenCostPack* pack, const double* F, int32_t r) {
+  if (pack == nullptr || F == nullptr || r < 1 || pack->lmi != nullptr) return RAYEN_E_BAD_ARG;
+  int rc = rayen::check_device(pack->device);
+  if (rc != RAYEN_OK) return rc;
+  rc = rayen::cost_lmi_build(F, r, pack->k, &pack->lmi);
+  if (rc == RAYEN_OK) pack->eq_shift = 1;
+  return rc;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the whole set at one precision: its rows (when it has any) and its LMI (when it has one)
+template <typename T>
+bool serves_set(const RayenCostPack* p) {
+  const bool rows = sizeof(T) == 8 ? p->served64 : p->served32;
+  if (p->n_rows > 0 && !rows) return false;
+  if (p->lmi != nullptr) return rayen::cost_lmi_serves<T>(p->lmi);
+  return p->n_rows > 0;
+}
+
+// the rows' launch, then the LMI's on the same stream (accumulating when the rows came first)
+template <typename T, typename Rows>
+int soft_cost(const RayenCostPack* pack, const T* y, int64_t B, int64_t ld, T* cost, T* worst, int32_t* which, T* grad,
+              int64_t ld_grad, void* stream, Rows&& launch_rows) {
+  int rc = check_call(pack, y, B, ld, grad, ld_grad);
+  if (rc != RAYEN_OK) return rc;
+  if (!serves_set<T>(pack)) return RAYEN_E_UNSUPPORTED;
+  const bool both = pack->lmi != nullptr && pack->n_rows > 0;
+  if (both && which != nullptr && worst == nullptr) return RAYEN_E_BAD_ARG;     // (the LMI's launch compares with the stored worst)
+  rc = rayen::check_device(pack->device);
+  if (rc != RAYEN_OK || B == 0) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (pack->n_rows > 0) {
+    rc = launch_rows(st);
+    if (rc != RAYEN_OK) return rc;
+  }
+  if (pack->lmi == nullptr) return RAYEN_OK;
+  return rayen::cost_lmi_launch<T>(pack->lmi, y, B, ld, cost, worst, which, grad, ld_grad, both ? 1 : 0, pack->lmi_id, st);
+}
+
+}  // namespace
+
+extern "C" {
+
 int rayen_cost_served(const RayenCostPack* pack, int32_t f64) {
   if (pack == nullptr) return 0;
-  return f64 ? (pack->served64 ? 1 : 0) : (pack->served32 ? 1 : 0);
+  return (f64 ? serves_set<double>(pack) : serves_set<float>(pack)) ? 1 : 0;
 }
 
 int rayen_soft_cost_f32(const RayenCostPack* pack, const float* y, int64_t B, int64_t ld, float* cost, float* worst,
                         int32_t* which, float* grad, int64_t ld_grad, void* stream) {
-  int rc = check_call(pack, y, B, ld, grad, ld_grad);
-  if (rc != RAYEN_OK) return rc;
-  if (!pack->served32) return RAYEN_E_UNSUPPORTED;
-  rc = rayen::check_device(pack->device);
-  if (rc != RAYEN_OK || B == 0) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return grad != nullptr ? launch32<true>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st)
-                         : launch32<false>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
+  return soft_cost<float>(pack, y, B, ld, cost, worst, which, grad, ld_grad, stream, [&](hipStream_t st) {
+    return grad != nullptr ? launch32<true>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st)
+                           : launch32<false>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
+  });
 }
 
 int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, int64_t ld, double* cost, double* worst,
                         int32_t* which, double* grad, int64_t ld_grad, void* stream) {
-  int rc = check_call(pack, y, B, ld, grad, ld_grad);
-  if (rc != RAYEN_OK) return rc;
-  if (!pack->served64) return RAYEN_E_UNSUPPORTED;
-  rc = rayen::check_device(pack->device);
-  if (rc != RAYEN_OK || B == 0) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return rayen::dispatch_width<kMinK64, kMaxK64>(pack->K64, [&](auto K) {
-    return launch64_k<K()>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
+  return soft_cost<double>(pack, y, B, ld, cost, worst, which, grad, ld_grad, stream, [&](hipStream_t st) {
+    return rayen::dispatch_width<kMinK64, kMaxK64>(pack->K64, [&](auto K) {
+      return launch64_k<K()>(pack, y, B, ld, cost, worst, which, grad, ld_grad, st);
+    });
   });
 }
 

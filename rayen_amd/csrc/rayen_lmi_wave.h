@@ -273,6 +273,70 @@ __global__ __launch_bounds__(64) void lmi_wave_kernel(
   if (nan_flag && bad) atomicOr(nan_flag, 1);
 }
 
+// eigenvector of lambda_max = `kap` of the matrix tridiagonalise() reduced (reflectors in A, tau), left in zz with unit
+// norm (shared by the backward below and by the soft cost of an LMI, rayen_cost_lmi.hip)
+template <typename T>
+__device__ __forceinline__ void top_eigenvector(T* A, const int LD, const int r, T* dd, T* ee, T* tau, T* vv, T* ww,
+                                                T* zz, const T kap, const int lane) {
+  // ---- eigenvector of the tridiagonal matrix: inverse iteration on M = (lam + shift) I - T = L D L' (every lane runs
+  // the O(r) recurrences redundantly; lane 0 writes)
+  T scale = fabs(kap);
+  for (int i = 0; i < r; ++i) scale = fmax(scale, fabs(dd[i]));
+  const T shift = Eps<T>::shift * fmax(scale, Eps<T>::tiny);
+  // ww: D of the factorisation, vv: the sub-diagonal of L (vv[i] couples rows i - 1 and i)
+  {
+    T dprev = fmax(kap + shift - dd[0], shift * T(1e-3));
+    if (lane == 0) { ww[0] = dprev; vv[0] = T(0); }
+    for (int i = 1; i < r; ++i) {
+      const T li = ee[i - 1] / dprev;              // M's off-diagonal is -ee: l = -ee / D, kept with the sign folded
+      const T di = fmax(kap + shift - dd[i] - li * ee[i - 1], shift * T(1e-3));
+      if (lane == 0) { vv[i] = -li; ww[i] = di; }
+      dprev = di;
+    }
+  }
+  for (int i = lane; i < r; i += 64) zz[i] = T(1) + T(0.01) * (T)i;   // not orthogonal to anything special
+  __syncthreads();
+  for (int it = 0; it < 3; ++it) {
+    if (lane == 0) {
+      for (int i = 1; i < r; ++i) zz[i] = fma(-vv[i], zz[i - 1], zz[i]);          // L y = b
+      zz[r - 1] = zz[r - 1] / ww[r - 1];
+      T nrm2 = zz[r - 1] * zz[r - 1];
+      for (int i = r - 2; i >= 0; --i) {                                            // D L' z = y
+        zz[i] = fma(-vv[i + 1], zz[i + 1], zz[i] / ww[i]);
+        nrm2 = fma(zz[i], zz[i], nrm2);
+      }
+      const T inv = T(1) / sqrt(fmax(nrm2, Eps<T>::tiny));
+      for (int i = 0; i < r; ++i) zz[i] *= inv;
+    }
+    __syncthreads();
+  }
+  // ---- x = H_0 H_1 ... H_{r-3} z
+  for (int c = r - 3; c >= 0; --c) {
+    const T tc = tau[c];
+    if (tc == T(0)) continue;                      // (wave-uniform)
+    T dot = T(0);
+    for (int i = c + 1 + lane; i < r; i += 64) dot = fma(A[i * LD + c], zz[i], dot);
+    dot = wsum(dot) * tc;
+    for (int i = c + 1 + lane; i < r; i += 64) zz[i] = fma(-dot, A[i * LD + c], zz[i]);
+    __syncthreads();
+  }
+}
+
+// A[idx] = x_i x_j of x = zz over the packed lower triangle, doubled off the diagonal: sum_idx G[idx] A[idx] = x' G x
+template <typename T>
+__device__ __forceinline__ void outer_product_packed(T* A, T* zz, const int P, const int lane) {
+  // (in packed order over the matrix storage: one contraction per generator follows)
+  __syncthreads();
+  for (int idx = lane; idx < P; idx += 64) {
+    int i = (int)((sqrtf(8.f * (float)idx + 1.f) - 1.f) * 0.5f);
+    while ((i + 1) * (i + 2) / 2 <= idx) ++i;
+    while (i * (i + 1) / 2 > idx) --i;
+    const int j = idx - i * (i + 1) / 2;
+    A[idx] = (i == j ? T(1) : T(2)) * zz[i] * zz[j];
+  }
+  __syncthreads();
+}
+
 //   grad_v = s t - [kappa > 1] s^2 (t . v) grad kappa(v),   t = NA_E' g,   s = 1 / max(1, kappa)
 template <typename T>
 __global__ __launch_bounds__(64) void lmi_wave_bwd_kernel(
@@ -321,58 +385,8 @@ __global__ __launch_bounds__(64) void lmi_wave_bwd_kernel(
   if (clipped && aseg == lmi_seg) {
     form_S<T>(A, LD, gt, vs, n, P, Pp, lane);
     tridiagonalise<T>(A, LD, r, dd, ee, tau, vv, ww, lane);
-    // ---- eigenvector of the tridiagonal matrix: inverse iteration on M = (lam + shift) I - T = L D L' (every lane runs
-    // the O(r) recurrences redundantly; lane 0 writes)
-    T scale = fabs(kap);
-    for (int i = 0; i < r; ++i) scale = fmax(scale, fabs(dd[i]));
-    const T shift = Eps<T>::shift * fmax(scale, Eps<T>::tiny);
-    // ww: D of the factorisation, vv: the sub-diagonal of L (vv[i] couples rows i - 1 and i)
-    {
-      T dprev = fmax(kap + shift - dd[0], shift * T(1e-3));
-      if (lane == 0) { ww[0] = dprev; vv[0] = T(0); }
-      for (int i = 1; i < r; ++i) {
-        const T li = ee[i - 1] / dprev;              // M's off-diagonal is -ee: l = -ee / D, kept with the sign folded
-        const T di = fmax(kap + shift - dd[i] - li * ee[i - 1], shift * T(1e-3));
-        if (lane == 0) { vv[i] = -li; ww[i] = di; }
-        dprev = di;
-      }
-    }
-    for (int i = lane; i < r; i += 64) zz[i] = T(1) + T(0.01) * (T)i;   // not orthogonal to anything special
-    __syncthreads();
-    for (int it = 0; it < 3; ++it) {
-      if (lane == 0) {
-        for (int i = 1; i < r; ++i) zz[i] = fma(-vv[i], zz[i - 1], zz[i]);          // L y = b
-        zz[r - 1] = zz[r - 1] / ww[r - 1];
-        T nrm2 = zz[r - 1] * zz[r - 1];
-        for (int i = r - 2; i >= 0; --i) {                                            // D L' z = y
-          zz[i] = fma(-vv[i + 1], zz[i + 1], zz[i] / ww[i]);
-          nrm2 = fma(zz[i], zz[i], nrm2);
-        }
-        const T inv = T(1) / sqrt(fmax(nrm2, Eps<T>::tiny));
-        for (int i = 0; i < r; ++i) zz[i] *= inv;
-      }
-      __syncthreads();
-    }
-    // ---- x = H_0 H_1 ... H_{r-3} z
-    for (int c = r - 3; c >= 0; --c) {
-      const T tc = tau[c];
-      if (tc == T(0)) continue;                      // (wave-uniform)
-      T dot = T(0);
-      for (int i = c + 1 + lane; i < r; i += 64) dot = fma(A[i * LD + c], zz[i], dot);
-      dot = wsum(dot) * tc;
-      for (int i = c + 1 + lane; i < r; i += 64) zz[i] = fma(-dot, A[i * LD + c], zz[i]);
-      __syncthreads();
-    }
-    // ---- x_i x_j (twice off the diagonal) in packed order over the matrix storage, then one contraction per generator
-    __syncthreads();
-    for (int idx = lane; idx < P; idx += 64) {
-      int i = (int)((sqrtf(8.f * (float)idx + 1.f) - 1.f) * 0.5f);
-      while ((i + 1) * (i + 2) / 2 <= idx) ++i;
-      while (i * (i + 1) / 2 > idx) --i;
-      const int j = idx - i * (i + 1) / 2;
-      A[idx] = (i == j ? T(1) : T(2)) * zz[i] * zz[j];
-    }
-    __syncthreads();
+    top_eigenvector<T>(A, LD, r, dd, ee, tau, vv, ww, zz, kap, lane);
+    outer_product_packed<T>(A, zz, P, lane);
     for (int a = 0; a < n; ++a) {
       const T* col = gt + (size_t)a * Pp;
       T part = T(0);

@@ -800,11 +800,12 @@ euclid_project.register_autograd(_proj_backward, setup_context=_proj_setup_conte
 
 # ------------------------------------------------------------------------------------------------
 # soft cost and violation (examples/cost_computer.py:69-110, ConvexConstraints.getResiduals): loss + gradient on rayen_cost.hip
+# and, for a set's LMI, rayen_cost_lmi.hip
 # ------------------------------------------------------------------------------------------------
 
 class CostPack(_SidePack):
-    """Owner of one ``RayenCostPack*``: fp32 and fp64 images of a set's stacked rows (``soft_cost.set_arrays``) on one
-    device."""
+    """Owner of one ``RayenCostPack*``: fp32 and fp64 images of a set's stacked rows (``soft_cost.set_arrays``) and of its
+    LMI's generators, when it has one, on one device."""
     _layer = "cost"
 
     def __init__(self, arrays, device_index):
@@ -813,6 +814,10 @@ class CostPack(_SidePack):
         self._create(device_index, ptr(a["A1"]), ptr(a["b1"]), int(a["b1"].size), ptr(a["P"]), ptr(a["q"]), ptr(a["r"]),
                      int(a["r"].size), ptr(a["M"]), ptr(a["s"]), ptr(a["c"]), ptr(a["d"]), ptr(a["soc_rows"]),
                      int(a["soc_rows"].size), ptr(a["A2"]), ptr(a["b2"]), int(a["b2"].size), self.k)
+        if a["F"].size:          # the set's LMI: F [k + 1, r, r] (rayen_cost_lmi.hip)
+            with torch.cuda.device(self.device_index):
+                _lib.check(_entry("rayen_cost_pack_set_lmi")(self.handle, ptr(a["F"]), int(a["F"].shape[-1])),
+                           "rayen_cost_pack_set_lmi")
 
     def served(self, dtype):
         return bool(_entry("rayen_cost_served")(self.handle, int(dtype == torch.float64)))
@@ -820,7 +825,7 @@ class CostPack(_SidePack):
 
 def soft_cost_raw(y, pack, want_grad):
     """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``:
-    one launch."""
+    one launch (two for a set that has an LMI next to other constraints)."""
     _check_rows(y, pack.k, pack, "y", "cost")
     y = _dense_rows(y, pack.k)
     B = y.shape[0]

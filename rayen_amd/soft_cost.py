@@ -12,10 +12,12 @@ differentiable in ``y``.
 
 Tensors on a HIP device run ``rayen_amd/csrc/rayen_cost.hip`` through ``rayen_amd::soft_cost``: ONE launch reads ``y`` once
 and writes ``cost``, ``worst``, ``which`` and -- when ``y`` requires a gradient -- ``d cost[b] / d y[b]``, so the backward is
-``grad_out[:, None] * grad`` and nothing of size ``[B, rows]`` reaches memory.  The mirror below (the same formulas in plain
-torch ops, differentiated by autograd) serves host tensors, sets with an LMI (no LMI kernel work here: the eigenvalue and
-its gradient are ``torch.linalg.eigvalsh``'s) and sets the kernel refuses (one ``RuntimeWarning``; an error under
-``RAYEN_STRICT_HIP=1``).  16-bit inputs are computed in fp32.  A row with a NaN answers ``cost = worst = NaN``,
+``grad_out[:, None] * grad`` and nothing of size ``[B, rows]`` reaches memory.  A set's LMI runs on
+``rayen_amd/csrc/rayen_cost_lmi.hip`` (a wave per sample: the matrix in LDS, its extreme eigenvalue by Householder + Sturm
+multisection, the eigenvector only for samples outside): the only launch when the LMI is the set's only constraint, a second
+one that adds to the first one's outputs otherwise.  The mirror below (the same formulas in plain torch ops, differentiated by
+autograd; the LMI through ``torch.linalg.eigvalsh``) serves host tensors and sets the kernels refuse (one ``RuntimeWarning``;
+an error under ``RAYEN_STRICT_HIP=1``).  16-bit inputs are computed in fp32.  A row with a NaN answers ``cost = worst = NaN``,
 ``which = -1``; no other row is touched.
 """
 from __future__ import annotations
@@ -169,7 +171,7 @@ class SoftCost(nn.Module):
 
     def _evaluate(self, y2, want_grad):
         """``(cost, worst, which)`` of fp32 / fp64 rows: the kernel where it serves, the mirror elsewhere."""
-        if not y2.is_cuda or self.has_lmi_constraints or (y2.device.index, y2.dtype) in self._unsupported:
+        if not y2.is_cuda or (y2.device.index, y2.dtype) in self._unsupported:
             return self._mirror(y2)
         try:
             from . import ops
