@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 13
+#define RAYEN_ABI_VERSION 14
 
 enum {
   RAYEN_OK = 0,
@@ -426,6 +426,16 @@ typedef struct RayenProjPack RayenProjPack;
 int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv, const double* w0, int32_t n, int32_t m,
                            int32_t m_lin, const int32_t* soc_rows, int32_t n_soc, double rho, double sigma, double alpha,
                            RayenProjPack** out);
+/* ABI v14: a set with an LMI.  Its PSD block is the LAST r (r + 1) / 2 rows of G z + h in K, stored as svec: one row per
+ * (i, j) with i <= j, row-major ((0,0), (0,1), .., (0,r-1), (1,1), ..), off-diagonal rows scaled by sqrt(2) (the norm of the
+ * block is the Frobenius norm of the matrix), equilibrated by one scale.  rayen_proj_pack_create is then called with
+ * m_lin + sum soc_rows = m - r (r + 1) / 2 (fewer rows than m; more is RAYEN_E_BAD_ARG), and
+ * rayen_proj_pack_set_psd(pack, row0 = m - r (r + 1) / 2, r) claims the rest, once, before the first call; until then the
+ * forward and the backward return RAYEN_E_UNSUPPORTED.  One LMI per set (the reference takes one lmic).  Pi_K on the block
+ * is V max(lambda, 0) V' by a parallel cyclic Jacobi decomposition in LDS, one wave per sample; the block adds
+ * 96 + 3 r (r | 1) elements (rounded up to 4) of scratch per wave.  1 <= r <= 32 is staged; a larger block, or an image
+ * over the LDS budget with that scratch, returns RAYEN_E_UNSUPPORTED from the calls.  The workspace is unchanged. */
+int rayen_proj_pack_set_psd(RayenProjPack* pack, int32_t row0, int32_t r);
 void rayen_proj_pack_destroy(RayenProjPack* pack);
 int64_t rayen_proj_workspace_bytes(const RayenProjPack* pack, int64_t B, int32_t f64, int32_t backward);
 int rayen_proj_forward_f32(const RayenProjPack* pack, const float* q, int64_t B, int64_t ldq, float* z, int64_t ldz,

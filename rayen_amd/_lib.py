@@ -10,7 +10,7 @@ import os
 
 from ._build import LIBRARY
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 SEG_LIN, SEG_QUAD_SYM, SEG_QUAD_FAC, SEG_SOC, SEG_LMI = range(5)
 E_UNSUPPORTED = -6      # RAYEN_E_UNSUPPORTED (include/rayen_hip.h)
@@ -34,7 +34,7 @@ EXPORTS = (
     "rayen_bar_backward_f32", "rayen_bar_backward_f64",
     "rayen_dc3_pack_create", "rayen_dc3_pack_destroy", "rayen_dc3_workspace_bytes", "rayen_dc3_forward_f32",
     "rayen_dc3_forward_f64", "rayen_dc3_backward_f32", "rayen_dc3_backward_f64",
-    "rayen_proj_pack_create", "rayen_proj_pack_destroy", "rayen_proj_workspace_bytes", "rayen_proj_forward_f32",
+    "rayen_proj_pack_create", "rayen_proj_pack_set_psd", "rayen_proj_pack_destroy", "rayen_proj_workspace_bytes", "rayen_proj_forward_f32",
     "rayen_proj_forward_f64", "rayen_proj_backward_f32", "rayen_proj_backward_f64",
     "rayen_cost_pack_create", "rayen_cost_pack_set_lmi", "rayen_cost_pack_destroy", "rayen_cost_served", "rayen_soft_cost_f32", "rayen_soft_cost_f64",
 )
@@ -174,6 +174,8 @@ def load():
         getattr(lib, name).argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
     lib.rayen_proj_pack_create.restype = ctypes.c_int
     lib.rayen_proj_pack_create.argtypes = [p, p, p, p, i32, i32, i32, p, i32, f64, f64, f64, ctypes.POINTER(ctypes.c_void_p)]
+    lib.rayen_proj_pack_set_psd.restype = ctypes.c_int
+    lib.rayen_proj_pack_set_psd.argtypes = [p, i32, i32]
     lib.rayen_proj_pack_destroy.restype = None
     lib.rayen_proj_pack_destroy.argtypes = [p]
     lib.rayen_proj_workspace_bytes.restype = ctypes.c_int64

@@ -584,13 +584,14 @@ class ConvexConstraints:
             raise Exception(f"Value is not optimal, prob_status={info['status']}")
         return y.reshape(k, 1), float(np.sum((y - p) ** 2))
 
-    def projectBatch(self, Y, max_iters=4000, eps=None):
+    def projectBatch(self, Y, max_iters=4000, eps=None, lmi=False):
         """Batched :meth:`project`: ``Y [B, k]`` -> ``(Y_projected [B, k], squared distances [B])``.  A torch tensor stays
         on its device and dtype (a HIP device runs ``rayen_amd/csrc/rayen_proj.hip``); anything else is computed in fp64
         on the host and returned as numpy.  The point is split into its part in the equality subspace,
         ``z = NA_E'(y - yp)``, which ``projection.ProjectionModule.project`` projects, and the part orthogonal to it,
         whose squared norm adds to the distance (``NA_E`` has orthonormal columns).  ``eps``: the stop tolerance of the
-        iteration (default 1e-9 in fp64, 1e-6 below)."""
+        iteration (default 1e-9 in fp64, 1e-6 below).  ``lmi=True``: a set with an LMI is served (the default raises
+        ``NotImplementedError`` on one)."""
         import torch
         from . import projection
         as_numpy = not isinstance(Y, torch.Tensor)
@@ -598,7 +599,7 @@ class ConvexConstraints:
         Yt = Yt.reshape(-1, self.k)
         module = self.__dict__.get("_projection_module")
         if module is None:
-            module = self.__dict__["_projection_module"] = projection.ProjectionModule(self, create_map=False)
+            module = self.__dict__["_projection_module"] = projection.ProjectionModule(self, create_map=False, lmi=lmi)
         if eps is None:
             eps = 1e-9 if Yt.dtype == torch.float64 else 1e-6
         NA_E = torch.as_tensor(self.NA_E, dtype=Yt.dtype, device=Yt.device)

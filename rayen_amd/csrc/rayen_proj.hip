@@ -24,6 +24,29 @@
 // The iterations run in launches of kChunk; between launches (x, v) of the rows still running rest in the caller's
 // workspace, finished rows are skipped, a workgroup whose rows have all finished leaves before it stages the image.  No
 // host sync, no grid barrier, no atomics.
+//
+// A set with an LMI (rayen_proj_pack_set_psd) has ONE PSD block, the last r (r + 1) / 2 rows of v, stored as svec: one row
+// per (i, j) with i <= j, row-major ((0,0), (0,1), .., (0,r-1), (1,1), ..), the off-diagonal rows scaled by sqrt(2), so
+// that the norm of the block is the Frobenius norm of the matrix and Pi_K on it is V max(lambda, 0) V'.  "Has a PSD block"
+// is a template parameter: a set without one runs the instantiations it ran before.  The block adds per-wave LDS scratch:
+// an eigenvector matrix V, a working matrix A and a second working matrix (the backward's products), each r x (r | 1),
+// r eigenvalues and the (c, s) of a round's rotations.  1 <= r <= 32.
+//
+// Eigen-decomposition: parallel cyclic Jacobi by the wave, in LDS.  Round-robin over r' = r rounded up to even: r' - 1
+// rounds per sweep, r' / 2 disjoint pairs per round (a pair with the padding index is skipped).  Per round the pair owners
+// (lanes 0 .. r'/2 - 1) compute (c, s) with t = sign(tau) / (|tau| + sqrt(1 + tau^2)), tau = (a_qq - a_pp) / (2 a_pq); the
+// whole wave applies the row rotations to A, then the column rotations to A and V; wave_sync() between the steps.  The
+// sweep loop stops when the off-diagonal norm is <= tol ||A||_F (reduced over the wave: wave-uniform) or at kSweepCap, so
+// every loop has a bounded, wave-uniform trip count whatever the data; a NaN block never meets the test, runs to the cap
+// and answers NaN in its own row.  Cap and tol come from a HOST run of the same sweep (numpy, same ordering, same formulas,
+// same precision) on the PSD blocks of the seeded test cases (tests/proj_lmi_reference.py: G q + h and the mirror's v* of
+// every row, r = 1 .. 32): fp32, tol 1e-6 (the sweep's floor there is 2.4e-7): worst 7 sweeps -> cap 9; fp64, tol 1e-13
+// (floor 4.6e-16): worst 8 sweeps -> cap 10.  The off-diagonal norm bounds the error of the rebuilt projection.
+// Forward: the decomposition starts cold each iteration; a block whose eigenvalues are all >= 0 is copied (p == v bit for
+// bit: the 0-iteration contract of an interior row), otherwise each lane rebuilds its own rows of V max(lambda, 0) V' as
+// v - V min(lambda, 0) V' (r FMAs per row, sqrt(2) on the off-diagonals).
+// Backward: v*'s block is decomposed once per launch, V and lambda stay in the scratch, and each iteration computes
+// V (B o (V'HV)) V' with B_ij = 1 (both > 0), 0 (both <= 0), lambda_+ / (lambda_+ - lambda_-) (mixed; 0 counts as <= 0).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -35,11 +58,14 @@
 
 namespace {
 constexpr int kMaxSoc = 32;
+constexpr int kMaxPsd = 32;                   // largest PSD block served (r x r)
 }
 
 struct RayenProjPack {
   int device = -1, n = 0, m = 0, m_lin = 0, n_soc = 0;
   int16_t soc_row0[kMaxSoc] = {}, soc_rows[kMaxSoc] = {};
+  int psd_row0 = 0, psd_dim = 0;                // the PSD block (svec rows psd_row0 .. m - 1); psd_dim 0: none
+  int unclaimed = 0;                            // rows after the cones that rayen_proj_pack_set_psd has yet to claim
   double rho = 1.0, sigma = 1e-6, alpha = 1.6;
   float* img32 = nullptr;
   double* img64 = nullptr;
@@ -58,6 +84,7 @@ using rayen::kLdsBudget;                      // 256 bytes of it are left to sta
 struct Dims {
   int n, m, m_lin, n_soc, mpad;
   int off_K, off_h, off_w0, total, scratch;   // in elements of T; scratch: per wave
+  int psd_row0, psd_dim, psd_pad, psd_mat;    // the PSD block: its first row, r, r | 1, elements of one r x (r | 1) matrix
 };
 
 inline int round4(int x) { return (x + 3) & ~3; }
@@ -71,16 +98,19 @@ Dims dims_of(const RayenProjPack* p) {
   d.off_w0 = d.off_h + round4(p->m);
   d.total = d.off_w0 + round4(p->n);
   d.scratch = 128 + round4(p->m);             // xt / rhs [64], cone statistics [64], u [m]
+  d.psd_row0 = p->psd_row0; d.psd_dim = p->psd_dim; d.psd_pad = p->psd_dim | 1;
+  d.psd_mat = round4(p->psd_dim * d.psd_pad);
+  if (p->psd_dim > 0) d.scratch += 96 + 3 * d.psd_mat;      // rotations [64], lambda [32], V, A and the second work matrix
   return d;
 }
 
 size_t lds_bytes(const Dims& d, size_t elem) { return ((size_t)d.total + (size_t)kWaves * d.scratch) * elem; }
 
-// served(): the one rule.  n in lanes, m in kMaxR registers per lane, the cones in the argument block, the image and the
-// waves' scratch in LDS.
+// served(): the one rule.  n in lanes, m in kMaxR registers per lane, the cones in the argument block, the PSD block at
+// most kMaxPsd x kMaxPsd (its 528 svec rows count in m), the image and the waves' scratch in LDS.
 bool shape_served(const RayenProjPack* p, size_t elem) {
-  return p->n >= 1 && p->n <= kMaxN && p->m >= 1 && p->m <= kMaxRows && p->n_soc <= kMaxSoc &&
-         lds_bytes(dims_of(p), elem) <= kLdsBudget - 256;
+  return p->n >= 1 && p->n <= kMaxN && p->m >= 1 && p->m <= kMaxRows && p->n_soc <= kMaxSoc && p->unclaimed == 0 &&
+         p->psd_dim >= 0 && p->psd_dim <= kMaxPsd && lds_bytes(dims_of(p), elem) <= kLdsBudget - 256;
 }
 
 template <typename T> const T* image(const RayenProjPack* p);
@@ -141,7 +171,98 @@ __device__ __forceinline__ void cone_stats(const ProjArgs<T>& a, int c, int lane
   t = su[last];
 }
 
-template <typename T, int R, bool BWD>
+// ---- the PSD block -------------------------------------------------------------------------------------------------
+template <typename T> struct Jacobi;
+template <> struct Jacobi<float> { static constexpr int kSweepCap = 9; static constexpr float kTol2 = 1e-12f; };
+template <> struct Jacobi<double> { static constexpr int kSweepCap = 10; static constexpr double kTol2 = 1e-26; };
+
+// idx / r for 0 <= idx < 1024, 1 <= r <= 32 (exact: (idx + 1/2) / r is at least 1 / 64 away from an integer)
+__device__ __forceinline__ int div_small(int idx, float rinv) { return (int)(((float)idx + 0.5f) * rinv); }
+
+// pair k of round s of the round-robin over nm1 + 1 players: (p, q), p < q
+__device__ __forceinline__ void pair_of(int k, int s, int nm1, int& p, int& q) {
+  int x = k == 0 ? nm1 : (s + k) % nm1;
+  int y = k == 0 ? s : (s + nm1 - k) % nm1;
+  p = x < y ? x : y;
+  q = x < y ? y : x;
+}
+
+// A [r x rp] symmetric in LDS -> eigenvalues in lam[0..r), eigenvectors in the columns of V (A is destroyed).  fro2 is
+// ||A||_F^2.  Called by the whole wave; ends with a wave_sync().
+template <typename T>
+__device__ __forceinline__ void jacobi_eig(T* __restrict__ A, T* __restrict__ V, T* __restrict__ lam, T* __restrict__ rot,
+                                            int r, int rp, int lane, T fro2) {
+  const float rinv = 1.0f / (float)r;
+  const int rr = r * r;
+  for (int idx = lane; idx < rr; idx += 64) {
+    const int i = div_small(idx, rinv), j = idx - i * r;
+    V[i * rp + j] = i == j ? T(1) : T(0);
+  }
+  wave_sync();
+  const int r2 = (r + 1) & ~1, np = r2 >> 1, nm1 = r2 - 1;
+  for (int sweep = 0; sweep < Jacobi<T>::kSweepCap; ++sweep) {
+    T off2 = T(0);
+    for (int idx = lane; idx < rr; idx += 64) {
+      const int i = div_small(idx, rinv), j = idx - i * r;
+      const T x = A[i * rp + j];
+      off2 += i == j ? T(0) : x * x;
+    }
+    off2 = wave_sum(off2);
+    if (off2 <= Jacobi<T>::kTol2 * fro2) break;          // (wave-uniform; false on a NaN)
+    for (int s = 0; s < nm1; ++s) {
+      if (lane < np) {
+        int p, q;
+        pair_of(lane, s, nm1, p, q);
+        T c = T(1), sn = T(0);
+        if (q < r) {
+          const T apq = A[p * rp + q];
+          if (apq != T(0)) {
+            const T tau = (A[q * rp + q] - A[p * rp + p]) / (apq + apq);
+            const T t = (tau >= T(0) ? T(1) : T(-1)) / (fabs(tau) + sqrt(T(1) + tau * tau));
+            c = T(1) / sqrt(T(1) + t * t);
+            sn = t * c;
+          }
+        }
+        rot[2 * lane] = c;
+        rot[2 * lane + 1] = sn;
+      }
+      wave_sync();
+      // rows p and q of A <- J'A, one (pair, column) per item
+      for (int idx = lane; idx < np * r; idx += 64) {
+        const int k = div_small(idx, rinv), j = idx - k * r;
+        int p, q;
+        pair_of(k, s, nm1, p, q);
+        if (q < r) {
+          const T c = rot[2 * k], sn = rot[2 * k + 1];
+          const T ap = A[p * rp + j], aq = A[q * rp + j];
+          A[p * rp + j] = c * ap - sn * aq;
+          A[q * rp + j] = sn * ap + c * aq;
+        }
+      }
+      wave_sync();
+      // columns p and q of A <- A J and of V <- V J, one (pair, row) per item
+      for (int idx = lane; idx < np * r; idx += 64) {
+        const int k = div_small(idx, rinv), i = idx - k * r;
+        int p, q;
+        pair_of(k, s, nm1, p, q);
+        if (q < r) {
+          const T c = rot[2 * k], sn = rot[2 * k + 1];
+          const T ap = A[i * rp + p], aq = A[i * rp + q];
+          A[i * rp + p] = c * ap - sn * aq;
+          A[i * rp + q] = sn * ap + c * aq;
+          const T vp = V[i * rp + p], vq = V[i * rp + q];
+          V[i * rp + p] = c * vp - sn * vq;
+          V[i * rp + q] = sn * vp + c * vq;
+        }
+      }
+      wave_sync();
+    }
+  }
+  if (lane < r) lam[lane] = A[lane * rp + lane];
+  wave_sync();
+}
+
+template <typename T, int R, bool BWD, bool PSD>
 __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
   extern __shared__ __align__(16) unsigned char proj_smem[];
   __shared__ int sh_any;
@@ -175,6 +296,12 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
   T* sx = L + d.total + (size_t)wave * d.scratch;      // [64]
   T* sc = sx + 64;                                     // [64]: (s, t) of v* per cone (backward)
   T* su = sc + 64;                                     // [round4(m)]
+  T* rot = su + ((d.m + 3) & ~3);                          // [64]: (c, s) of a round's rotations          (PSD only)
+  T* lam = rot + 64;                                   // [32]: eigenvalues
+  T* Vm = lam + 32;                                    // [r x rp]: eigenvectors (the backward: of v*, kept)
+  T* Am = Vm + d.psd_mat;                              // [r x rp]: working matrix
+  T* Tm = Am + d.psd_mat;                              // [r x rp]: second working matrix (the backward's products)
+  const int pr = d.psd_dim, prp = d.psd_pad;
   const int n = d.n, m = d.m, mpad = d.mpad;
   const bool own = lane < n;
   const T w0j = (!BWD && own) ? L[d.off_w0 + lane] : T(0);
@@ -188,6 +315,36 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
     off[r] = valid[r] ? i : m - 1;
     hr[r] = BWD ? T(0) : hh[off[r]];
   }
+  // (i, j) of the svec rows this lane holds: i | j << 8, or -1 for a row outside the block
+  int pij[PSD ? R : 1];
+  if constexpr (PSD) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int rem = lane + 64 * r - d.psd_row0, i = 0;
+      const bool in = rem >= 0 && valid[r];
+      for (int k = 0; k < pr; ++k)
+        if (rem >= pr - i) { rem -= pr - i; ++i; }
+      pij[r] = in ? (i | ((i + rem) << 8)) : -1;
+    }
+  }
+  const T kSqrt2 = T(1.4142135623730951), kRsqrt2 = T(0.7071067811865476);
+  // Am = smat of the block of the vector in w[]; returns ||block||^2 (= ||Am||_F^2)
+  auto psd_smat = [&](const T (&w)[R]) -> T {
+    T part = T(0);
+    if constexpr (PSD) {
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if (pij[r] >= 0) {
+          const int i = pij[r] & 255, j = pij[r] >> 8;
+          const T x = i == j ? w[r] : w[r] * kRsqrt2;
+          Am[i * prp + j] = x;
+          Am[j * prp + i] = x;
+          part += w[r] * w[r];
+        }
+      part = wave_sum(part);
+    }
+    return part;
+  };
   const int t0 = a.chunk * kChunk;
   const int t_end = a.max_iters - t0 < kChunk ? a.max_iters : t0 + kChunk;
 
@@ -221,6 +378,12 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
         if (lane == 0) { sc[2 * c] = s; sc[2 * c + 1] = t; }
       }
       wave_sync();
+      if constexpr (PSD) {
+        // V and lambda of v*'s block: kept for every iteration of this launch
+        const T fro2 = psd_smat(vs);
+        wave_sync();
+        jacobi_eig<T>(Am, Vm, lam, rot, pr, prp, lane, fro2);
+      }
     } else {
       rhs2 = inj * T(2);
     }
@@ -272,6 +435,68 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
             if (i >= row0 && i < last) p[r] = inside ? v[r] : (zero ? T(0) : mid);
             if (i == last) p[r] = inside ? dt : (zero ? T(0) : da);
           }
+        }
+      }
+      if constexpr (PSD) {
+        const T fro2 = psd_smat(v);
+        wave_sync();
+        if constexpr (!BWD) {
+          jacobi_eig<T>(Am, Vm, lam, rot, pr, prp, lane, fro2);
+          const bool bad = lane < pr && !(lam[lane] >= T(0));
+          if (__any(bad)) {
+            // this lane's rows of V max(lambda, 0) V', taken as v - V min(lambda, 0) V': the same matrix, but what the
+            // sweep's rounding (V'V - I is 3e-6 at r = 20 in fp32) multiplies is the negative part alone, not ||A||; with
+            // the sum over the positive part the fp32 iteration at r >= 20 jitters above its stop rule and never ends
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+              if (pij[r] >= 0) {
+                const int i = pij[r] & 255, j = pij[r] >> 8;
+                T sum = T(0);
+                for (int k = 0; k < pr; ++k) sum = fma(Vm[i * prp + k] * fmax(-lam[k], T(0)), Vm[j * prp + k], sum);
+                p[r] = v[r] + (i == j ? sum : sum * kSqrt2);
+              }
+          } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+              if (pij[r] >= 0) p[r] = v[r];
+          }
+        } else {
+          // V (B o (V'HV)) V' with H = Am: Tm = V'H, Am = B o (Tm V), Tm = V Am, rows of Tm V'
+          const float rinv = 1.0f / (float)pr;
+          const int rr = pr * pr;
+          for (int idx = lane; idx < rr; idx += 64) {
+            const int i = div_small(idx, rinv), j = idx - i * pr;
+            T sum = T(0);
+            for (int k = 0; k < pr; ++k) sum = fma(Vm[k * prp + i], Am[k * prp + j], sum);
+            Tm[i * prp + j] = sum;
+          }
+          wave_sync();
+          for (int idx = lane; idx < rr; idx += 64) {
+            const int i = div_small(idx, rinv), j = idx - i * pr;
+            T sum = T(0);
+            for (int k = 0; k < pr; ++k) sum = fma(Tm[i * prp + k], Vm[k * prp + j], sum);
+            const T li = lam[i], lj = lam[j];
+            const bool pi = li > T(0), pj = lj > T(0);
+            const T hi = fmax(li, lj), lo = fmin(li, lj);
+            const T b = (pi && pj) ? T(1) : ((pi != pj) ? hi / (hi - lo) : T(0));
+            Am[i * prp + j] = (li == li && lj == lj) ? b * sum : li + lj;          // (a NaN eigenvalue is handed on)
+          }
+          wave_sync();
+          for (int idx = lane; idx < rr; idx += 64) {
+            const int i = div_small(idx, rinv), j = idx - i * pr;
+            T sum = T(0);
+            for (int k = 0; k < pr; ++k) sum = fma(Vm[i * prp + k], Am[k * prp + j], sum);
+            Tm[i * prp + j] = sum;
+          }
+          wave_sync();
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            if (pij[r] >= 0) {
+              const int i = pij[r] & 255, j = pij[r] >> 8;
+              T sum = T(0);
+              for (int k = 0; k < pr; ++k) sum = fma(Tm[i * prp + k], Vm[j * prp + k], sum);
+              p[r] = i == j ? sum : sum * kSqrt2;
+            }
         }
       }
     };
@@ -399,10 +624,10 @@ __global__ __launch_bounds__(kThreads) void proj_kernel(const ProjArgs<T> a) {
   }
 }
 
-template <typename T, int R, bool BWD>
-int launch(const RayenProjPack* p, ProjArgs<T> a, hipStream_t stream) {
+template <typename T, int R, bool BWD, bool PSD>
+int launch_as(const RayenProjPack* p, ProjArgs<T> a, hipStream_t stream) {
   const size_t lds = lds_bytes(a.d, sizeof(T));
-  auto kern = proj_kernel<T, R, BWD>;
+  auto kern = proj_kernel<T, R, BWD, PSD>;
   if (!rayen::allow_lds(kern, lds)) return RAYEN_E_LAUNCH;
   const int64_t groups = (a.B + kWaves - 1) / kWaves;
   int64_t per_cu = (int64_t)(kLdsBudget / (lds + 256));
@@ -415,6 +640,11 @@ int launch(const RayenProjPack* p, ProjArgs<T> a, hipStream_t stream) {
     if (hipGetLastError() != hipSuccess) return RAYEN_E_LAUNCH;
   }
   return RAYEN_OK;
+}
+
+template <typename T, int R, bool BWD>
+int launch(const RayenProjPack* p, ProjArgs<T> a, hipStream_t stream) {
+  return p->psd_dim > 0 ? launch_as<T, R, BWD, true>(p, a, stream) : launch_as<T, R, BWD, false>(p, a, stream);
 }
 
 template <typename T, bool BWD>
@@ -480,7 +710,7 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
     if (soc_rows[c] < 1) return RAYEN_E_BAD_ARG;
     rows += soc_rows[c];
   }
-  if (rows != m) return RAYEN_E_BAD_ARG;
+  if (rows > m) return RAYEN_E_BAD_ARG;        // rows < m: the rest is a PSD block that rayen_proj_pack_set_psd claims
   int dev = -1;
   if (rayen::side_pack_device(&dev) != RAYEN_OK) return RAYEN_E_NO_DEVICE;
   RayenProjPack* p = new (std::nothrow) RayenProjPack();
@@ -488,8 +718,12 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
   p->device = dev;
   p->n = n; p->m = m; p->m_lin = m_lin; p->n_soc = n_soc;
   p->rho = rho; p->sigma = sigma; p->alpha = alpha;
+  p->psd_row0 = m;
   *out = p;
-  if (n > kMaxN || m > kMaxRows || n_soc > kMaxSoc) return RAYEN_OK;      // not staged: every call answers RAYEN_E_UNSUPPORTED
+  if (n > kMaxN || m > kMaxRows || n_soc > kMaxSoc) {                     // not staged: every call answers RAYEN_E_UNSUPPORTED
+    p->unclaimed = (int)(m - rows);
+    return RAYEN_OK;
+  }
   int at = m_lin;
   for (int c = 0; c < n_soc; ++c) {
     p->soc_row0[c] = (int16_t)at;
@@ -504,6 +738,21 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
     *out = nullptr;
     return RAYEN_E_ALLOC;
   }
+  p->unclaimed = (int)(m - rows);                // (> 0: not served until rayen_proj_pack_set_psd claims the block)
+  return RAYEN_OK;
+}
+
+int rayen_proj_pack_set_psd(RayenProjPack* p, int32_t row0, int32_t r) {
+  if (p == nullptr || r < 1 || r > 32767 || p->psd_dim != 0 || p->unclaimed == 0 || row0 != p->m - p->unclaimed ||
+      (int64_t)r * (r + 1) / 2 != p->unclaimed)
+    return RAYEN_E_BAD_ARG;
+  p->psd_row0 = row0;
+  p->psd_dim = r;
+  p->unclaimed = 0;
+  // the block's scratch counts against the LDS budget: an image that no longer fits is dropped (RAYEN_E_UNSUPPORTED)
+  rayen::DeviceScope on_device(p->device);
+  if (p->img32 && !shape_served(p, sizeof(float))) { (void)hipFree(p->img32); p->img32 = nullptr; }
+  if (p->img64 && !shape_served(p, sizeof(double))) { (void)hipFree(p->img64); p->img64 = nullptr; }
   return RAYEN_OK;
 }
 

@@ -717,6 +717,10 @@ class ProjPack(_SidePack):
         self.n, self.m = int(a["n"]), int(a["m"])
         self._create(device_index, ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]), ptr(a["w0"]), self.n, self.m, int(a["m_lin"]),
                      ptr(a["soc_rows"]), int(a["soc_rows"].size), float(a["rho"]), float(a["sigma"]), float(a["alpha"]))
+        if int(a.get("psd_dim", 0)):          # the set's LMI: the last rows of G are its PSD block, svec
+            with torch.cuda.device(self.device_index):
+                _lib.check(_entry("rayen_proj_pack_set_psd")(self.handle, int(a["psd_row0"]), int(a["psd_dim"])),
+                           "rayen_proj_pack_set_psd")
 
 
 def proj_forward_raw(q, pack, max_iters, eps):

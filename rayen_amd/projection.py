@@ -4,7 +4,8 @@
 The core is ``Pi(q) = argmin ||z - q||^2`` subject to ``A_p z <= b_p`` and the quadratics and cones evaluated at
 ``y = NA_E z + yp`` -- the reference's program, which it hands to cvxpylayers + ECOS one sample at a time.  Here it is the
 operator-splitting iteration of ``rayen_amd/conic.py`` specialised to ``P = 2I, c = -2q``: the cone rows ``G z + h in K``
-(slack of ``A_p`` as orthant rows, every quadratic and SOC as a second-order cone) are the same for the whole batch, so
+(slack of ``A_p`` as orthant rows, every quadratic and SOC as a second-order cone, the LMI as a PSD block) are the same for
+the whole batch, so
 the rows are assembled and equilibrated, ``rho`` is chosen and ``K^-1 = ((2 + sigma) I + rho G'G)^-1`` is formed ONCE per
 set, in fp64 on the host (:func:`build_program`).  With ``v = z_r + y / rho + h`` the splitting variables are
 ``z = Pi_K(v) - h`` and ``y = rho (v - Pi_K(v))`` (Moreau), so the state of a sample is ``(x, v)`` and one iteration is
@@ -26,6 +27,12 @@ place of ``2 q`` -- run to the same stop rule on ``g`` scaled to unit maximum.
 Tensors on a HIP device run ``rayen_amd/csrc/rayen_proj.hip`` through ``rayen_amd::euclid_project``; host tensors, and sets
 the kernel does not stage (one ``RuntimeWarning``; an error under ``RAYEN_STRICT_HIP=1``), run the mirror below: the same
 iteration in plain torch ops.  It is the eager path, not the test reference (tests/proj_reference.py).
+
+A set with an LMI is served on request (``lmi=True``; the default still raises ``NotImplementedError``).  Its PSD block
+comes LAST in ``G z + h in K`` and is stored as svec: ``r (r + 1) / 2`` rows, one per ``(i, j)`` with ``i <= j``, row-major
+(``(0,0), (0,1), .., (0,r-1), (1,1), ..``), the off-diagonal rows scaled by ``sqrt(2)``.  The Euclidean norm of the block
+is then the Frobenius norm of the matrix and ``Pi_K`` on it is the Euclidean projection onto the PSD cone
+(``V max(lambda, 0) V'``); the block is equilibrated by ONE scale, like a second-order cone.
 """
 from __future__ import annotations
 
@@ -47,12 +54,21 @@ DEFAULT_MAX_ITERS, DEFAULT_EPS = 512, 1e-6
 # the program of a set (host, fp64, once)
 # ------------------------------------------------------------------------------------------------------------------
 
-def cone_rows(cs):
-    """``(G [m, n], h [m], m_lin, soc_rows)`` of ``G z + h in K``, unscaled: ``m_lin`` orthant rows first (the slack of
-    ``A_p``; rows of zeros are dropped), then one second-order cone per quadratic and per SOC (``t`` stored last)."""
-    if cs.has_lmi_constraints:
-        raise NotImplementedError("the Euclidean projection serves linear, quadratic and second-order-cone constraints; "
-                                  "a set with an LMI needs a PSD projection per iteration, which is not built")
+def svec_index(r):
+    """``(i [rows], j [rows], scale [rows])`` of the svec storage of a symmetric ``r x r`` block: ``i <= j``, row-major;
+    ``scale`` is 1 on the diagonal and ``sqrt(2)`` off it."""
+    i, j = np.triu_indices(r)
+    return i, j, np.where(i == j, 1.0, np.sqrt(2.0))
+
+
+def cone_rows(cs, lmi=False):
+    """``(G [m, n], h [m], m_lin, soc_rows, psd_dim)`` of ``G z + h in K``, unscaled: ``m_lin`` orthant rows first (the
+    slack of ``A_p``; rows of zeros are dropped), then one second-order cone per quadratic and per SOC (``t`` stored
+    last), then, with ``lmi=True``, the LMI's ``psd_dim x psd_dim`` block in svec storage (0: the set has none)."""
+    if cs.has_lmi_constraints and not lmi:
+        raise NotImplementedError("the Euclidean projection serves linear, quadratic and second-order-cone constraints by "
+                                  "default; a set with an LMI needs a PSD projection per iteration and is served on request: "
+                                  "pass lmi=True")
     prog = conic.ConeProgram(cs.n)
     keep = np.any(cs.A_p != 0.0, axis=1)
     prog.add(conic.NONNEG, -cs.A_p[keep], cs.b_p[keep, 0])
@@ -60,17 +76,25 @@ def cone_rows(cs):
     cs._nonlinear_cone_rows(prog, cs.NA_E, cs.yp)
     G, h = prog.stacked()
     soc_rows = [rows for kind, rows, _ in prog.cones if kind == conic.SOC]
-    return G, h, m_lin, soc_rows
+    psd_dim = 0
+    if cs.has_lmi_constraints:                # the rows of cs._nonlinear_cone_rows (full r x r storage) folded to svec
+        psd_dim = int(prog.cones[-1][2])
+        full = G.shape[0] - psd_dim * psd_dim
+        i, j, scale = svec_index(psd_dim)
+        fold = lambda a: 0.5 * scale.reshape((-1,) + (1,) * (a.ndim - 1)) * (a[full + i * psd_dim + j] + a[full + j * psd_dim + i])   # noqa: E731
+        G, h = np.concatenate((G[:full], fold(G)), axis=0), np.concatenate((h[:full], fold(h)))
+    return G, h, m_lin, soc_rows, psd_dim
 
 
-def _equilibrate(G, h, m_lin, soc_rows):
-    """One scale per orthant row and per cone block (``conic.solve``'s rule: a cone stays a cone)."""
+def _equilibrate(G, h, m_lin, soc_rows, psd_dim=0):
+    """One scale per orthant row and per cone block, the PSD block included (``conic.solve``'s rule: a cone stays a
+    cone)."""
     scale = np.ones(G.shape[0])
     Gh = np.concatenate((G, h[:, None]), axis=1)
     rn = np.linalg.norm(Gh[:m_lin], axis=1)
     scale[:m_lin] = 1.0 / np.where(rn > 0, rn, 1.0)
     at = m_lin
-    for rows in soc_rows:
+    for rows in list(soc_rows) + ([psd_dim * (psd_dim + 1) // 2] if psd_dim else []):
         nrm = float(np.linalg.norm(Gh[at:at + rows])) / np.sqrt(rows)
         if nrm > 0:
             scale[at:at + rows] = 1.0 / nrm
@@ -81,9 +105,11 @@ def _equilibrate(G, h, m_lin, soc_rows):
 class Program:
     """The per-set constants of the iteration, fp64 numpy (picklable)."""
 
-    def __init__(self, G, h, m_lin, soc_rows, n, rho):
+    def __init__(self, G, h, m_lin, soc_rows, n, rho, psd_dim=0):
         self.G, self.h, self.m_lin, self.soc_rows, self.n = G, h, int(m_lin), [int(r) for r in soc_rows], int(n)
         self.m = int(G.shape[0])
+        self.psd_dim = int(psd_dim)              # the PSD block: the last psd_dim (psd_dim + 1) / 2 rows, svec
+        self.psd_row0 = self.m - self.psd_dim * (self.psd_dim + 1) // 2
         self.set_rho(rho)
 
     def set_rho(self, rho):
@@ -98,7 +124,7 @@ class Program:
         c = np.ascontiguousarray
         return dict(G=c(self.G), h=c(self.h), Kinv=c(self.Kinv), w0=c(self.w0), m_lin=self.m_lin,
                     soc_rows=np.asarray(self.soc_rows, dtype=np.int32), n=self.n, m=self.m, rho=self.rho,
-                    sigma=SIGMA, alpha=ALPHA)
+                    sigma=SIGMA, alpha=ALPHA, psd_row0=self.psd_row0, psd_dim=self.psd_dim)
 
 
 def probe_points(cs, count=8, seed=0):
@@ -108,22 +134,29 @@ def probe_points(cs, count=8, seed=0):
     return z0 + (1.0 + float(np.max(np.abs(z0)))) * rng.standard_normal((count, cs.n))
 
 
-def build_program(cs, rho=None, probe_eps=1e-8, probe_iters=2000):
+def build_program(cs, rho=None, probe_eps=1e-8, probe_iters=2000, lmi=False):
     """Assemble, equilibrate and pick ``rho``: the candidate with the fewest iterations (worst probe row, fp64 mirror at
-    ``probe_eps``) wins; ties go to the value nearest 1.  ``rho`` given: taken as is."""
-    G, h, m_lin, soc_rows = cone_rows(cs)
-    G, h = _equilibrate(G, h, m_lin, soc_rows)
-    prog = Program(G, h, m_lin, soc_rows, cs.n, 1.0 if rho is None else rho)
+    ``probe_eps``) wins; ties go to the value nearest 1.  ``rho`` given: taken as is.  ``lmi=True``: a set with an LMI is
+    served (its PSD block last, svec); the default raises ``NotImplementedError`` on one."""
+    G, h, m_lin, soc_rows, psd_dim = cone_rows(cs, lmi=lmi)
+    G, h = _equilibrate(G, h, m_lin, soc_rows, psd_dim)
+    prog = Program(G, h, m_lin, soc_rows, cs.n, 1.0 if rho is None else rho, psd_dim)
     if rho is not None:
         return prog
-    q = torch.from_numpy(probe_points(cs))
-    best = None
-    for cand in RHO_CANDIDATES:
-        prog.set_rho(cand)
-        _, iters, _ = mirror_forward(Constants(prog, torch.float64, q.device), q, probe_iters, probe_eps)
-        key = (int(iters.max()), abs(np.log(cand)))
-        if best is None or key < best[0]:
-            best = (key, cand)
+    q0, z0 = probe_points(cs), np.asarray(cs.z0, dtype=np.float64).reshape(1, cs.n)
+    for spread in (1.0, 4.0, 16.0, 64.0):
+        q = torch.from_numpy(z0 + spread * (q0 - z0))
+        best = None
+        for cand in RHO_CANDIDATES:
+            prog.set_rho(cand)
+            _, iters, _ = mirror_forward(Constants(prog, torch.float64, q.device), q, probe_iters, probe_eps)
+            key = (int(iters.max()), abs(np.log(cand)))
+            if best is None or key < best[0]:
+                best = (key, cand)
+        # a set with an LMI is often wide around z0 (F_k dominates): probes that all fall inside say nothing about rho,
+        # so they are spread further until one leaves (sets without an LMI keep the one round they have always had)
+        if best[0][0] > 0 or not psd_dim:
+            break
     prog.set_rho(best[1])
     prog.probe_iters = best[0][0]
     return prog
@@ -149,6 +182,62 @@ class Constants:
         i64 = lambda a: torch.as_tensor(a, dtype=torch.int64, device=device)              # noqa: E731
         self.idx_x, self.cid_x, self.idx_t = i64(idx_x), i64(cid_x), i64(idx_t)
         self.n_soc = len(prog.soc_rows)
+        self.psd_dim, self.psd_row0 = getattr(prog, "psd_dim", 0), getattr(prog, "psd_row0", prog.m)
+        if self.psd_dim:
+            i, j, scale = svec_index(self.psd_dim)
+            self.psd_i, self.psd_j, self.psd_scale = i64(i), i64(j), t(scale)
+
+
+def smat(c, block):
+    """``[B, r (r + 1) / 2]`` svec rows -> ``[B, r, r]`` symmetric matrices."""
+    M = block.new_zeros(block.shape[0], c.psd_dim, c.psd_dim)
+    w = block / c.psd_scale
+    M[:, c.psd_i, c.psd_j] = w
+    M[:, c.psd_j, c.psd_i] = w
+    return M
+
+
+def svec(c, M):
+    return M[:, c.psd_i, c.psd_j] * c.psd_scale
+
+
+def psd_eig(c, v):
+    """``(lambda [B, r] ascending, V [B, r, r], finite [B])`` of the PSD block of ``v``; a row with a NaN or an infinity is
+    decomposed as zeros and answers NaN in its own block only."""
+    block = v[:, c.psd_row0:]
+    finite = torch.isfinite(block).all(dim=1)
+    lam, V = torch.linalg.eigh(smat(c, torch.where(finite[:, None], block, torch.zeros_like(block))))
+    return lam, V, finite
+
+
+def _psd_project(c, v):
+    """The block of ``Pi_K(v)``: ``svec(V max(lambda, 0) V')``, computed as ``v - svec(V min(lambda, 0) V')`` -- the same
+    matrix, but the rounding of the decomposition then multiplies the negative part alone and not ``||A||``: with the sum
+    over the positive part the fp32 iteration at ``r >= 20`` jitters about its stop rule (one host took 614 iterations on
+    a row of the 32 x 32 test case, another 3759; the kernel ran to ``max_iters``).  A block with every eigenvalue ``>= 0``
+    is handed back as it is, bit for bit (an interior row's ``p == v_raw`` rests on it)."""
+    lam, V, finite = psd_eig(c, v)
+    block = v[:, c.psd_row0:]
+    rebuilt = block + svec(c, (V * torch.clamp_min(-lam, 0.0)[:, None, :]) @ V.transpose(1, 2))
+    out = torch.where((lam >= 0).all(dim=1)[:, None], block, rebuilt)
+    return torch.where(finite[:, None], out, torch.full_like(out, float("nan")))
+
+
+def _psd_weights(lam):
+    """``B_ij`` of ``D Pi(M)[H] = V (B o (V'HV)) V'``: 1 where both eigenvalues are ``> 0``, 0 where both are ``<= 0``,
+    ``lambda_+ / (lambda_+ - lambda_-)`` on a mixed pair (an eigenvalue of exactly 0 counts as ``<= 0``)."""
+    li, lj = lam[:, :, None], lam[:, None, :]
+    pi, pj = li > 0, lj > 0
+    hi, lo = torch.maximum(li, lj), torch.minimum(li, lj)
+    mixed = hi / torch.where(pi ^ pj, hi - lo, torch.ones_like(hi))
+    return torch.where(pi & pj, torch.ones_like(hi), torch.where(pi ^ pj, mixed, torch.zeros_like(hi)))
+
+
+def _psd_derivative(c, eig, dv):
+    lam, V, finite = eig
+    T = V.transpose(1, 2) @ smat(c, dv[:, c.psd_row0:]) @ V
+    out = svec(c, V @ (_psd_weights(lam) * T) @ V.transpose(1, 2))
+    return torch.where(finite[:, None], out, torch.full_like(out, float("nan")))
 
 
 def _soc_parts(c, v):
@@ -167,11 +256,14 @@ def cone_project(c, v):
         coef = torch.where(inside, torch.ones_like(s), torch.where(zero, torch.zeros_like(s), a / s))
         out[:, c.idx_x] = x * coef[:, c.cid_x]
         out[:, c.idx_t] = torch.where(inside, t, torch.where(zero, torch.zeros_like(t), a))
+    if c.psd_dim:
+        out[:, c.psd_row0:] = _psd_project(c, v)
     return out
 
 
-def cone_derivative(c, v, dv):
-    """``D Pi_K(v) dv`` (an element of the generalised Jacobian on a kink)."""
+def cone_derivative(c, v, dv, eig=None):
+    """``D Pi_K(v) dv`` (an element of the generalised Jacobian on a kink).  ``eig``: ``psd_eig(c, v)`` when the caller
+    has it (the backward decomposes ``v*`` once)."""
     out = torch.where(v > 0, dv, torch.zeros_like(dv))
     if c.n_soc:
         x, t, s = _soc_parts(c, v)
@@ -186,6 +278,8 @@ def cone_derivative(c, v, dv):
         ins_x, zer_x = inside[:, c.cid_x], zero[:, c.cid_x]
         out[:, c.idx_x] = torch.where(ins_x, dx, torch.where(zer_x, torch.zeros_like(dx), mid_x))
         out[:, c.idx_t] = torch.where(inside, dt, torch.where(zero, torch.zeros_like(dt), da))
+    if c.psd_dim:
+        out[:, c.psd_row0:] = _psd_derivative(c, psd_eig(c, v) if eig is None else eig, dv)
     return out
 
 
@@ -236,7 +330,8 @@ def mirror_backward(c, g, vstar, iters, max_iters, eps):
     scale = _rowmax(g)
     scale = torch.where(scale > 0, scale, torch.ones_like(scale))[:, None]
     gn = g / scale
-    D = lambda dv: cone_derivative(c, vstar, dv)                # noqa: E731
+    eig = psd_eig(c, vstar) if c.psd_dim else None
+    D = lambda dv: cone_derivative(c, vstar, dv, eig)           # noqa: E731
     out, _, _ = _iterate(c, 2.0 * gn, gn, D(gn @ c.G.T), interior, int(max_iters), eps, D, 0.0, 0.0)
     return torch.where(interior[:, None], g, out * scale)
 
@@ -265,10 +360,11 @@ class _MirrorProject(torch.autograd.Function):
 class ProjectionModule(torch.nn.Module):
     """``mode='PP'``: ``y = NA_E Pi(q) + yp`` in training and eval.  ``mode='UP'``: ``z = q`` while ``self.training``,
     ``Pi(q)`` otherwise (rayen/constraint_module.py:488-504).  Same mapper contract and buffer names as
-    ``ConstraintModule``; ``project(q)`` returns ``(z, iters)``."""
+    ``ConstraintModule``; ``project(q)`` returns ``(z, iters)``.  ``lmi=True`` serves a set with an LMI (the default
+    raises ``NotImplementedError`` on one)."""
 
     def __init__(self, cs, input_dim=None, mode='PP', create_map=True, max_iters=DEFAULT_MAX_ITERS, eps=DEFAULT_EPS,
-                 rho=None):
+                 rho=None, lmi=False):
         super().__init__()
         if mode not in ('PP', 'UP'):
             raise ValueError(f"mode must be 'PP' or 'UP', got {mode!r}")
@@ -276,7 +372,7 @@ class ProjectionModule(torch.nn.Module):
             raise ValueError(f"max_iters must be an integer >= 1, got {max_iters!r}")
         if not float(eps) >= 0.0:
             raise ValueError(f"eps must be >= 0, got {eps!r}")
-        self.program = build_program(cs, rho=rho)          # (raises NotImplementedError on an LMI)
+        self.program = build_program(cs, rho=rho, lmi=lmi)          # (raises NotImplementedError on an LMI without lmi=True)
         self.mode, self.max_iters, self.eps = mode, int(max_iters), float(eps)
         self.cs = cs
         self.k, self.n = cs.k, cs.n
