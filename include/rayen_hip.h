@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define RAYEN_ABI_VERSION 14
+#define RAYEN_ABI_VERSION 15
 
 enum {
   RAYEN_OK = 0,
@@ -450,6 +450,11 @@ int rayen_proj_backward_f32(const RayenProjPack* pack, const float* g, int64_t B
 int rayen_proj_backward_f64(const RayenProjPack* pack, const double* g, int64_t B, int64_t ldg, const double* vstar,
                             const int32_t* iters, double* grad_q, int64_t ldgq, double eps, int32_t max_iters, void* ws,
                             int64_t ws_bytes, void* stream);
+
+/* ABI v15: the same projection on tiles of 32 samples on the matrix cores (rayen_proj_tile.hip): five more entry points,
+ * declared in rayen_hip_tile.h, which is part of this header (tests/test_proj_tile_host.py holds it against the binding's
+ * EXPORTS_TILE and links the five from C). */
+#include "rayen_hip_tile.h"
 
 /* ---- Soft cost and violation of a batch (ABI v12): the reference's training loss of UU / UP / DC3
  * (examples/cost_computer.py:69-110) and the residual metric every method is judged by, loss AND gradient in one launch

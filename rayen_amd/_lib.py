@@ -10,7 +10,7 @@ import os
 
 from ._build import LIBRARY
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 SEG_LIN, SEG_QUAD_SYM, SEG_QUAD_FAC, SEG_SOC, SEG_LMI = range(5)
 E_UNSUPPORTED = -6      # RAYEN_E_UNSUPPORTED (include/rayen_hip.h)
@@ -38,6 +38,10 @@ EXPORTS = (
     "rayen_proj_forward_f64", "rayen_proj_backward_f32", "rayen_proj_backward_f64",
     "rayen_cost_pack_create", "rayen_cost_pack_set_lmi", "rayen_cost_pack_destroy", "rayen_cost_served", "rayen_soft_cost_f32", "rayen_soft_cost_f64",
 )
+# ABI v15, declared in include/rayen_hip_tile.h (which rayen_hip.h includes); tests/test_proj_tile_host.py holds the two
+# against each other
+EXPORTS_TILE = ("rayen_proj_tile_layout", "rayen_proj_tile_served", "rayen_proj_tile_workspace_bytes",
+                "rayen_proj_tile_forward_f32", "rayen_proj_tile_backward_f32")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
 
@@ -186,6 +190,16 @@ def load():
     for name in ("rayen_proj_backward_f32", "rayen_proj_backward_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, i64, p, i32p, p, i64, f64, i32, p, i64, p]
+    lib.rayen_proj_tile_layout.restype = ctypes.c_int
+    lib.rayen_proj_tile_layout.argtypes = [i32, p, i32, i32p, p, p]
+    lib.rayen_proj_tile_served.restype = ctypes.c_int
+    lib.rayen_proj_tile_served.argtypes = [p]
+    lib.rayen_proj_tile_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_proj_tile_workspace_bytes.argtypes = [p, i64, i32]
+    lib.rayen_proj_tile_forward_f32.restype = ctypes.c_int
+    lib.rayen_proj_tile_forward_f32.argtypes = [p, p, i64, i64, p, i64, i32p, p, f64, i32, p, i64, p]
+    lib.rayen_proj_tile_backward_f32.restype = ctypes.c_int
+    lib.rayen_proj_tile_backward_f32.argtypes = [p, p, i64, i64, p, i32p, p, i64, f64, i32, p, i64, p]
     lib.rayen_cost_pack_create.restype = ctypes.c_int
     lib.rayen_cost_pack_create.argtypes = [p, p, i32, p, p, p, i32, p, p, p, p, p, i32, p, p, i32, i32,
                                            ctypes.POINTER(ctypes.c_void_p)]

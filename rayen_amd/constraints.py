@@ -584,14 +584,15 @@ class ConvexConstraints:
             raise Exception(f"Value is not optimal, prob_status={info['status']}")
         return y.reshape(k, 1), float(np.sum((y - p) ** 2))
 
-    def projectBatch(self, Y, max_iters=4000, eps=None, lmi=False):
+    def projectBatch(self, Y, max_iters=4000, eps=None, lmi=False, kernel='wave'):
         """Batched :meth:`project`: ``Y [B, k]`` -> ``(Y_projected [B, k], squared distances [B])``.  A torch tensor stays
         on its device and dtype (a HIP device runs ``rayen_amd/csrc/rayen_proj.hip``); anything else is computed in fp64
         on the host and returned as numpy.  The point is split into its part in the equality subspace,
         ``z = NA_E'(y - yp)``, which ``projection.ProjectionModule.project`` projects, and the part orthogonal to it,
         whose squared norm adds to the distance (``NA_E`` has orthonormal columns).  ``eps``: the stop tolerance of the
         iteration (default 1e-9 in fp64, 1e-6 below).  ``lmi=True``: a set with an LMI is served (the default raises
-        ``NotImplementedError`` on one)."""
+        ``NotImplementedError`` on one).  ``kernel``: ``'wave'`` (the default), ``'tile'`` or ``'auto'``, as in
+        ``projection.ProjectionModule``."""
         import torch
         from . import projection
         as_numpy = not isinstance(Y, torch.Tensor)
@@ -607,7 +608,7 @@ class ConvexConstraints:
         with torch.no_grad():
             zin = (Yt - yp) @ NA_E
             off = Yt - (zin @ NA_E.T + yp)
-            z, _ = module.project(zin, max_iters=max_iters, eps=eps)
+            z, _ = module.project(zin, max_iters=max_iters, eps=eps, kernel=kernel)
             out = z @ NA_E.T + yp
             dist = ((z - zin) ** 2).sum(dim=1) + (off ** 2).sum(dim=1)
         if as_numpy:

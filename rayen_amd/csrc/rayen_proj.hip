@@ -54,22 +54,12 @@
 #include <new>
 #include <vector>
 
-#include "rayen_side_pack.h"
+#include "rayen_proj_pack.h"
 
 namespace {
-constexpr int kMaxSoc = 32;
+constexpr int kMaxSoc = rayen::kProjMaxSoc;
 constexpr int kMaxPsd = 32;                   // largest PSD block served (r x r)
 }
-
-struct RayenProjPack {
-  int device = -1, n = 0, m = 0, m_lin = 0, n_soc = 0;
-  int16_t soc_row0[kMaxSoc] = {}, soc_rows[kMaxSoc] = {};
-  int psd_row0 = 0, psd_dim = 0;                // the PSD block (svec rows psd_row0 .. m - 1); psd_dim 0: none
-  int unclaimed = 0;                            // rows after the cones that rayen_proj_pack_set_psd has yet to claim
-  double rho = 1.0, sigma = 1e-6, alpha = 1.6;
-  float* img32 = nullptr;
-  double* img64 = nullptr;
-};
 
 namespace {
 
@@ -720,6 +710,8 @@ int rayen_proj_pack_create(const double* G, const double* h, const double* Kinv,
   p->rho = rho; p->sigma = sigma; p->alpha = alpha;
   p->psd_row0 = m;
   *out = p;
+  // the tile kernel's images (rayen_proj_tile.hip): where its envelope holds and no row is left for a PSD block
+  if (rows == m) p->tile = rayen::proj_tile_create(G, h, Kinv, w0, n, m, m_lin, soc_rows, n_soc);
   if (n > kMaxN || m > kMaxRows || n_soc > kMaxSoc) {                     // not staged: every call answers RAYEN_E_UNSUPPORTED
     p->unclaimed = (int)(m - rows);
     return RAYEN_OK;
@@ -762,6 +754,7 @@ void rayen_proj_pack_destroy(RayenProjPack* p) {
     rayen::DeviceScope on_device(p->device);
     if (p->img32) (void)hipFree(p->img32);
     if (p->img64) (void)hipFree(p->img64);
+    rayen::proj_tile_destroy(p->tile);
   }
   delete p;
 }

@@ -483,7 +483,7 @@ def _host_ptr(x):
     return x.ctypes.data if x.size else None
 
 
-def _workspace(pack, t, backward, max_steps=None):
+def _workspace(pack, t, backward, max_steps=None, tile=False):
     """``(scratch tensor, its size for the library)`` of a DC3 call (``max_steps`` given) or a projection call on the rows
     of ``t``, as ``rayen_*_workspace_bytes`` sizes it; refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read here, at
     call time)."""
@@ -492,8 +492,13 @@ def _workspace(pack, t, backward, max_steps=None):
         name, limit, extra = "rayen_dc3_workspace_bytes", DC3_MAX_WORKSPACE_BYTES, 0
         nbytes = int(_entry(name)(pack.handle, B, int(max_steps), f64, int(backward)))
     else:
-        name, limit, extra = "rayen_proj_workspace_bytes", PROJ_MAX_WORKSPACE_BYTES, B * pack.m * t.element_size()   # (v*)
-        nbytes = int(_entry(name)(pack.handle, B, f64, int(backward)))
+        limit, extra = PROJ_MAX_WORKSPACE_BYTES, B * pack.m * t.element_size()   # (v*)
+        if tile:
+            name = "rayen_proj_tile_workspace_bytes"
+            nbytes = int(_entry(name)(pack.handle, B, int(backward)))
+        else:
+            name = "rayen_proj_workspace_bytes"
+            nbytes = int(_entry(name)(pack.handle, B, f64, int(backward)))
     if nbytes < 0:
         raise RuntimeError(f"rayen_amd: {name} refused its arguments")
     if nbytes + extra > limit:
@@ -723,33 +728,52 @@ class ProjPack(_SidePack):
                            "rayen_proj_pack_set_psd")
 
 
-def proj_forward_raw(q, pack, max_iters, eps):
-    """``(z [B, n], iters [B] int32, vstar [B, m])`` through ``rayen_proj_forward_*``."""
+PROJ_KERNELS = ("wave", "tile")
+
+
+def _proj_entry(direction, kernel, dtype):
+    """The library entry of ``kernel``: ``'wave'`` is rayen_proj.hip (wave per sample), ``'tile'`` rayen_proj_tile.hip (32
+    samples per workgroup on the matrix cores; fp32 only: an fp64 call is refused with ``E_UNSUPPORTED``)."""
+    if kernel not in PROJ_KERNELS:
+        raise ValueError(f"kernel must be one of {PROJ_KERNELS}, got {kernel!r}")
+    if kernel == "wave":
+        return _typed(f"rayen_proj_{direction}", dtype)
+    if dtype != torch.float32:
+        raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_proj_tile_{direction}")
+    return _entry(f"rayen_proj_tile_{direction}_f32")
+
+
+def proj_forward_raw(q, pack, max_iters, eps, kernel='wave'):
+    """``(z [B, n], iters [B] int32, vstar [B, m])`` through ``rayen_proj_forward_*`` (``kernel='tile'``:
+    ``rayen_proj_tile_forward_f32``)."""
     _check_rows(q, pack.n, pack, "q", "proj")
+    entry = _proj_entry("forward", kernel, q.dtype)
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
     z = torch.empty((B, pack.n), dtype=q.dtype, device=q.device)
     iters = torch.empty((B,), dtype=torch.int32, device=q.device)
     vstar = torch.empty((B, pack.m), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, False)
-        code = _typed("rayen_proj_forward", q.dtype)(
+        ws, nbytes = _workspace(pack, q, False, tile=kernel == "tile")
+        code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(z), pack.n, _ptr(iters), _ptr(vstar),
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(q.device.index))
     _lib.check(code, "rayen_proj_forward")
     return z, iters, vstar
 
 
-def proj_backward_raw(grad_z, vstar, iters, pack, max_iters, eps):
-    """``grad_q [B, n] = J grad_z`` row by row through ``rayen_proj_backward_*``."""
+def proj_backward_raw(grad_z, vstar, iters, pack, max_iters, eps, kernel='wave'):
+    """``grad_q [B, n] = J grad_z`` row by row through ``rayen_proj_backward_*`` (``kernel='tile'``:
+    ``rayen_proj_tile_backward_f32``); ``vstar`` and ``iters`` may come from either kernel's forward."""
     _check_rows(grad_z, pack.n, pack, "grad_z", "proj")
+    entry = _proj_entry("backward", kernel, grad_z.dtype)
     g = _dense_rows(grad_z, pack.n)
     vstar, iters = vstar.contiguous(), iters.contiguous()
     B = g.shape[0]
     grad_q = torch.empty((B, pack.n), dtype=g.dtype, device=g.device)
     with _on_device(g.device):
-        ws, nbytes = _workspace(pack, g, True)
-        code = _typed("rayen_proj_backward", g.dtype)(
+        ws, nbytes = _workspace(pack, g, True, tile=kernel == "tile")
+        code = entry(
             pack.handle, _ptr(g), B, g.stride(0) if B else pack.n, _ptr(vstar), _ptr(iters), _ptr(grad_q), pack.n,
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(g.device.index))
     _lib.check(code, "rayen_proj_backward")
@@ -800,6 +824,63 @@ def _proj_backward(ctx, grad_z, grad_iters, grad_vstar):
 
 
 euclid_project.register_autograd(_proj_backward, setup_context=_proj_setup_context)
+
+
+def proj_wave_served(pack, dtype):
+    """Does the wave kernel (rayen_proj.hip) stage this pack's program at ``dtype``?  Asked with an empty batch: the
+    library answers ``E_UNSUPPORTED`` before it would launch anything."""
+    with torch.cuda.device(pack.device_index):
+        code = _typed("rayen_proj_forward", dtype)(pack.handle, None, 0, pack.n, None, pack.n, None, None, 1e-6, 1, None, 0,
+                                                   None)
+    if code == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(code, "rayen_proj_forward")
+    return True
+
+
+def proj_tile_served(pack):
+    """Does the tile kernel hold this pack's program (its envelope: ``tile_served()`` in rayen_proj_tile.hip)?"""
+    return bool(_entry("rayen_proj_tile_served")(pack.handle))
+
+
+@torch.library.custom_op("rayen_amd::euclid_project_tile", mutates_args=())
+def euclid_project_tile(q: torch.Tensor, pack_id: int, max_iters: int,
+                        eps: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``euclid_project`` on the tile kernel (rayen_proj_tile.hip)."""
+    return proj_forward_raw(q, _pack(pack_id), max_iters, eps, kernel="tile")
+
+
+@euclid_project_tile.register_fake
+def _(q, pack_id, max_iters, eps):
+    pack = _pack(pack_id)
+    B = q.shape[0]
+    return q.new_empty((B, pack.n)), q.new_empty((B,), dtype=torch.int32), q.new_empty((B, pack.m))
+
+
+@torch.library.custom_op("rayen_amd::euclid_project_tile_bwd", mutates_args=())
+def euclid_project_tile_bwd(grad_z: torch.Tensor, vstar: torch.Tensor, iters: torch.Tensor, pack_id: int, max_iters: int,
+                            eps: float) -> torch.Tensor:
+    return proj_backward_raw(grad_z, vstar, iters, _pack(pack_id), max_iters, eps, kernel="tile")
+
+
+@euclid_project_tile_bwd.register_fake
+def _(grad_z, vstar, iters, pack_id, max_iters, eps):
+    return grad_z.new_empty((grad_z.shape[0], _pack(pack_id).n))
+
+
+def _proj_tile_backward(ctx, grad_z, grad_iters, grad_vstar):
+    vstar, iters = ctx.saved_tensors
+    if grad_z is None:
+        return None, None, None, None
+    pack = _pack(ctx.pack_id)
+    grad_q = torch.ops.rayen_amd.euclid_project_tile_bwd(grad_z.to(vstar.dtype), vstar, iters, ctx.pack_id, ctx.max_iters,
+                                                         ctx.eps)
+    if ctx.width > pack.n:          # columns of q beyond n are not read
+        grad_q = torch.nn.functional.pad(grad_q, (0, ctx.width - pack.n))
+    return grad_q, None, None, None
+
+
+euclid_project_tile.register_autograd(_proj_tile_backward, setup_context=_proj_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------

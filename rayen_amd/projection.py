@@ -28,6 +28,11 @@ Tensors on a HIP device run ``rayen_amd/csrc/rayen_proj.hip`` through ``rayen_am
 the kernel does not stage (one ``RuntimeWarning``; an error under ``RAYEN_STRICT_HIP=1``), run the mirror below: the same
 iteration in plain torch ops.  It is the eager path, not the test reference (tests/proj_reference.py).
 
+``kernel='tile'`` sends fp32 device tensors to ``rayen_amd/csrc/rayen_proj_tile.hip`` instead (tiles of 32 samples on the
+matrix cores: no LDS image, so programs beyond the wave kernel's 576 rows and 32 cones; no fp64, no LMI), ``kernel='auto'``
+does so only where the wave kernel refuses the set; what the chosen kernel refuses takes the same loud detour.  The default
+``'wave'`` is what every call ran before.
+
 A set with an LMI is served on request (``lmi=True``; the default still raises ``NotImplementedError``).  Its PSD block
 comes LAST in ``G z + h in K`` and is stored as svec: ``r (r + 1) / 2`` rows, one per ``(i, j)`` with ``i <= j``, row-major
 (``(0,0), (0,1), .., (0,r-1), (1,1), ..``), the off-diagonal rows scaled by ``sqrt(2)``.  The Euclidean norm of the block
@@ -361,13 +366,19 @@ class ProjectionModule(torch.nn.Module):
     """``mode='PP'``: ``y = NA_E Pi(q) + yp`` in training and eval.  ``mode='UP'``: ``z = q`` while ``self.training``,
     ``Pi(q)`` otherwise (rayen/constraint_module.py:488-504).  Same mapper contract and buffer names as
     ``ConstraintModule``; ``project(q)`` returns ``(z, iters)``.  ``lmi=True`` serves a set with an LMI (the default
-    raises ``NotImplementedError`` on one)."""
+    raises ``NotImplementedError`` on one).  ``kernel``: ``'wave'`` (rayen_proj.hip, the default), ``'tile'``
+    (rayen_proj_tile.hip) or ``'auto'`` (the wave kernel where it serves the set, the tile kernel where only it does)."""
+
+    KERNELS = ('wave', 'tile', 'auto')
 
     def __init__(self, cs, input_dim=None, mode='PP', create_map=True, max_iters=DEFAULT_MAX_ITERS, eps=DEFAULT_EPS,
-                 rho=None, lmi=False):
+                 rho=None, lmi=False, kernel='wave'):
         super().__init__()
         if mode not in ('PP', 'UP'):
             raise ValueError(f"mode must be 'PP' or 'UP', got {mode!r}")
+        if kernel not in self.KERNELS:
+            raise ValueError(f"kernel must be one of {self.KERNELS}, got {kernel!r}")
+        self.kernel = kernel
         if isinstance(max_iters, bool) or int(max_iters) != max_iters or int(max_iters) < 1:
             raise ValueError(f"max_iters must be an integer >= 1, got {max_iters!r}")
         if not float(eps) >= 0.0:
@@ -398,6 +409,7 @@ class ProjectionModule(torch.nn.Module):
         self.__dict__["_proj_packs"] = {}
         self.__dict__["_constants"] = {}
         self.__dict__["_unsupported"] = set()
+        self.__dict__["_auto_kernel"] = {}
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -406,7 +418,7 @@ class ProjectionModule(torch.nn.Module):
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        state["_proj_packs"], state["_constants"], state["_unsupported"] = {}, {}, set()
+        state["_proj_packs"], state["_constants"], state["_unsupported"], state["_auto_kernel"] = {}, {}, set(), {}
         state.pop("proj_iters", None)
         return state
 
@@ -434,23 +446,44 @@ class ProjectionModule(torch.nn.Module):
     def _mirror(self, q2, max_iters, eps):
         return _MirrorProject.apply(q2, self.constants(q2.dtype, q2.device), max_iters, eps)
 
-    def project(self, q, max_iters=None, eps=None):
+    def _device_kernel(self, kernel, pack, dtype):
+        """``'wave'`` or ``'tile'`` for this call.  ``'auto'``: the wave kernel wherever it serves the set at this
+        precision (asked of the library with an empty batch: nothing is launched), else the tile kernel where it does,
+        else the wave kernel, whose refusal is the one reported.  No timing enters."""
+        if kernel != 'auto':
+            return kernel
+        from . import ops
+        key = (pack.device_index, dtype)
+        cache = self.__dict__.setdefault("_auto_kernel", {})
+        chosen = cache.get(key)                              # (fixed per pack and precision: asked once)
+        if chosen is None:
+            tile = not ops.proj_wave_served(pack, dtype) and dtype == torch.float32 and ops.proj_tile_served(pack)
+            chosen = cache[key] = 'tile' if tile else 'wave'
+        return chosen
+
+    def project(self, q, max_iters=None, eps=None, kernel=None):
         """``q [B, n]`` (or ``[B, n, 1]``) -> ``(z [B, n], iters [B] int32)``: the projection in the subspace and the
         iterations each row took (0: ``q`` was inside; ``max_iters``: the row did not meet the stop rule).
-        ``max_iters`` / ``eps``: this call's, in place of the module's."""
+        ``max_iters`` / ``eps`` / ``kernel``: this call's, in place of the module's."""
         max_iters = self.max_iters if max_iters is None else int(max_iters)
         eps = self.eps if eps is None else float(eps)
+        kernel = getattr(self, "kernel", "wave") if kernel is None else kernel      # (a module pickled before `kernel` existed)
+        if kernel not in self.KERNELS:
+            raise ValueError(f"kernel must be one of {self.KERNELS}, got {kernel!r}")
         q2 = torch.flatten(q, 1)[:, :self.n]
         if q2.dtype not in (torch.float32, torch.float64):
-            z, iters = self.project(q2.float(), max_iters, eps)         # 16-bit activations: computed in fp32
+            z, iters = self.project(q2.float(), max_iters, eps, kernel)         # 16-bit activations: computed in fp32
             return z.to(q2.dtype), iters
-        if not q2.is_cuda or (q2.device.index, q2.dtype) in self._unsupported:
+        if not q2.is_cuda or (q2.device.index, q2.dtype, kernel) in self._unsupported:
             return self._mirror(q2, max_iters, eps)
         try:
             from . import ops
             pack, pack_id = self.proj_pack(q2.device)
+            chosen = self._device_kernel(kernel, pack, q2.dtype)
             if not (torch.is_grad_enabled() and q2.requires_grad):
-                z, iters, _ = ops.proj_forward_raw(q2, pack, max_iters, eps)
+                z, iters, _ = ops.proj_forward_raw(q2, pack, max_iters, eps, kernel=chosen)
+            elif chosen == 'tile':
+                z, iters, _ = torch.ops.rayen_amd.euclid_project_tile(q2, pack_id, max_iters, eps)
             else:
                 z, iters, _ = torch.ops.rayen_amd.euclid_project(q2, pack_id, max_iters, eps)
             return z, iters
@@ -460,7 +493,7 @@ class ProjectionModule(torch.nn.Module):
             warnings.warn(f"rayen_amd: no HIP kernel serves this projection ({err}); this module now runs the same "
                           "iteration in torch ops (rayen_amd/projection.py) on " + str(q2.device), RuntimeWarning,
                           stacklevel=3)
-            self._unsupported.add((q2.device.index, q2.dtype))
+            self._unsupported.add((q2.device.index, q2.dtype, kernel))
             return self._mirror(q2, max_iters, eps)
 
     def forward(self, x):
