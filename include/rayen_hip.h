@@ -397,6 +397,12 @@ int rayen_dc3_backward_f64(const RayenDc3Pack* pack, const double* q, int64_t B,
                            int64_t ldg, double* grad_q, int64_t ldgq, double lr, double momentum, int32_t max_steps,
                            const int32_t* tstar, void* ws, int64_t ws_bytes, void* stream);
 
+/* The DC3 tile kernels (additive to ABI v15: rayen_dc3_tile_shape_served, rayen_dc3_tile_pack_set, rayen_dc3_tile_served,
+ * rayen_dc3_tile_workspace_bytes, rayen_dc3_tile_forward_f32, rayen_dc3_tile_backward_f32) are declared, with their
+ * contract, in rayen_hip_dc3_tile.h, which is part of this header (tests/test_dc3_tile_host.py holds it against the binding's
+ * EXPORTS_DC3_TILE and links it from plain C). */
+#include "rayen_hip_dc3_tile.h"
+
 /* ---- Euclidean projection onto the set (ABI v11): the core of the reference's PP / UP layers
  * (rayen/constraint_module.py:76-96 and :488-504), batched and differentiable
  *

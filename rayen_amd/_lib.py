@@ -42,6 +42,10 @@ EXPORTS = (
 # against each other
 EXPORTS_TILE = ("rayen_proj_tile_layout", "rayen_proj_tile_served", "rayen_proj_tile_workspace_bytes",
                 "rayen_proj_tile_forward_f32", "rayen_proj_tile_backward_f32")
+# additive to ABI v15, declared in include/rayen_hip_dc3_tile.h (which rayen_hip.h includes, like rayen_hip_tile.h);
+# tests/test_dc3_tile_host.py holds the two against each other
+EXPORTS_DC3_TILE = ("rayen_dc3_tile_shape_served", "rayen_dc3_tile_pack_set", "rayen_dc3_tile_served",
+                    "rayen_dc3_tile_workspace_bytes", "rayen_dc3_tile_forward_f32", "rayen_dc3_tile_backward_f32")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
 
@@ -176,6 +180,18 @@ def load():
     for name in ("rayen_dc3_backward_f32", "rayen_dc3_backward_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
+    lib.rayen_dc3_tile_shape_served.restype = ctypes.c_int
+    lib.rayen_dc3_tile_shape_served.argtypes = [i32, i32, i32, i32]
+    lib.rayen_dc3_tile_pack_set.restype = ctypes.c_int
+    lib.rayen_dc3_tile_pack_set.argtypes = [p, p, p, p, p, p, p, p]
+    lib.rayen_dc3_tile_served.restype = ctypes.c_int
+    lib.rayen_dc3_tile_served.argtypes = [p]
+    lib.rayen_dc3_tile_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_dc3_tile_workspace_bytes.argtypes = [p, i64, i32, i32]
+    lib.rayen_dc3_tile_forward_f32.restype = ctypes.c_int
+    lib.rayen_dc3_tile_forward_f32.argtypes = [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]
+    lib.rayen_dc3_tile_backward_f32.restype = ctypes.c_int
+    lib.rayen_dc3_tile_backward_f32.argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
     lib.rayen_proj_pack_create.restype = ctypes.c_int
     lib.rayen_proj_pack_create.argtypes = [p, p, p, p, i32, i32, i32, p, i32, f64, f64, f64, ctypes.POINTER(ctypes.c_void_p)]
     lib.rayen_proj_pack_set_psd.restype = ctypes.c_int

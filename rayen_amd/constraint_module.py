@@ -20,7 +20,8 @@ is free; ``'Bar'`` (the barycentric baseline, :124-132 and :479-486) converts th
 vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kernel per direction
 (``rayen_amd/csrc/rayen_bar.hip``); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
 quadratic sets only) needs ``args_DC3`` and runs its fixed iteration, batch-global stop included, on
-``rayen_amd/csrc/rayen_dc3.hip`` (host side: ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
+``rayen_amd/csrc/rayen_dc3.hip`` or, with ``args_DC3['kernel'] = 'tile' | 'auto'``, ``rayen_dc3_tile.hip`` (host side:
+``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
 ``NotImplementedError`` here: they are served by a module of their own, ``rayen_amd.projection.ProjectionModule``.
 
 Documented deviation: for an SOC whose ray never meets the cone (negative
@@ -59,7 +60,15 @@ class ConstraintModule(torch.nn.Module):
 
     def _refused(self, v, old_head=False):
         refused = self.__dict__.get("_unsupported")
-        return bool(refused) and (None in refused or (v.device.index, v.dtype, bool(old_head)) in refused)
+        return bool(refused) and (None in refused or (v.device.index, v.dtype, self._route_key(old_head)) in refused)
+
+    def _route_key(self, old_head=False):
+        """Third part of a refusal's key: the old head of RAYEN_old, the kernel ``args_DC3`` asks for (``False`` for the
+        default, ``'lane'``), ``False`` otherwise."""
+        if self.method == 'DC3':
+            kernel = _dc3.kernel_choice(self.args_DC3)
+            return False if kernel == 'lane' else kernel
+        return bool(old_head)
 
     def __setattr__(self, name, value):
         super().__setattr__(name, value)
@@ -384,7 +393,34 @@ class ConstraintModule(torch.nn.Module):
         if entry is None:
             dp = ops.Dc3Pack(_dc3.pack_arrays(self), index)
             entry = packs[index] = (dp, ops.register_pack(dp))
+            # what 'tile' / 'auto' need from the device is settled here, with the pack's own uploads (like them, not while
+            # a stream is capturing): the calls after the first only look the answers up
+            kernel = self.dc3_kernel
+            if kernel == 'tile':
+                dp.tile_images()
+            elif kernel == 'auto':
+                for dtype in (torch.float32, torch.float64):
+                    self._dc3_kernel_for(dp, dtype)
         return entry
+
+    @property
+    def dc3_kernel(self):
+        """What ``args_DC3['kernel']`` asks for: ``'lane'`` (the default, rayen_dc3.hip), ``'tile'`` (rayen_dc3_tile.hip)
+        or ``'auto'``."""
+        return _dc3.kernel_choice(self.args_DC3)
+
+    def _dc3_kernel_for(self, dp, dtype):
+        """The kernel a call at ``dtype`` runs.  ``'auto'``: the lane kernel wherever it serves the pack at ``dtype``, else
+        the tile kernel where it does (fp32), else the lane kernel, whose refusal is then the one reported.  No timing
+        enters the choice."""
+        kernel = self.dc3_kernel
+        if kernel != 'auto':
+            return kernel
+        if ops.dc3_lane_served(dp, dtype):
+            return 'lane'
+        if dtype == torch.float32 and ops.dc3_tile_served(dp):
+            return 'tile'
+        return 'lane'
 
     def obtainyoFromypDC3(self, yp):
         return self.A2oi @ (self.b2_DC3 - self.A2p @ yp)
@@ -409,8 +445,11 @@ class ConstraintModule(torch.nn.Module):
         limit = _dc3.max_steps(self)
         try:
             dp, pack_id = self.dc3_pack(q2.device)
+            kernel = self._dc3_kernel_for(dp, q2.dtype)
             if not (torch.is_grad_enabled() and q2.requires_grad) and not torch.compiler.is_compiling():
-                y, steps = ops.dc3_forward_raw(q2, dp, lr, momentum, eps, limit)      # plain inference: straight to the C ABI
+                y, steps = ops.dc3_forward_raw(q2, dp, lr, momentum, eps, limit, kernel)      # plain inference: straight to the C ABI
+            elif kernel == 'tile':
+                y, steps = torch.ops.rayen_amd.dc3_project_tile(q2, pack_id, lr, momentum, eps, limit)
             else:
                 y, steps = torch.ops.rayen_amd.dc3_project(q2, pack_id, lr, momentum, eps, limit)
         except _lib.RayenError as err:
@@ -418,7 +457,7 @@ class ConstraintModule(torch.nn.Module):
                 raise
             warnings.warn(f"rayen_amd: no HIP kernel serves this DC3 layer ({err}); this module now runs the reference "
                           "formula with torch ops on " + str(q2.device), RuntimeWarning, stacklevel=3)
-            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, False))
+            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, self._route_key()))
             return self._dc3_reference(q2.unsqueeze(2))
         self.__dict__["dc3_steps"] = steps      # [1] int32 on q's device: the steps this call took (every route sets it)
         return y.unsqueeze(2)

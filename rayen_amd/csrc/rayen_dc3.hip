@@ -32,14 +32,7 @@
 #include <new>
 #include <vector>
 
-#include "rayen_side_pack.h"
-
-struct RayenDc3Pack {
-  int device = -1, k = 0, n = 0, m = 0, nq = 0, no = 0, NP = 0;
-  float* img32 = nullptr;
-  double* img64 = nullptr;
-  int32_t* perm = nullptr;      // [n] partial variables, then [no] other variables
-};
+#include "rayen_dc3_pack.h"
 
 namespace {
 
@@ -597,6 +590,7 @@ void rayen_dc3_pack_destroy(RayenDc3Pack* p) {
     if (p->img32) (void)hipFree(p->img32);
     if (p->img64) (void)hipFree(p->img64);
     if (p->perm) (void)hipFree(p->perm);
+    if (p->tile_img) (void)hipFree(p->tile_img);
   }
   delete p;
 }

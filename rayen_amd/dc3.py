@@ -15,11 +15,13 @@ import torch
 from . import utils
 
 ARG_KEYS = ("lr", "momentum", "eps_converge", "max_steps_training", "max_steps_testing")
+KERNEL_CHOICES = ("lane", "tile", "auto")      # the optional key args_DC3['kernel']; absent: 'lane'
 
 
 def check_args(args_DC3):
     """``args_DC3`` needs the five keys of the reference; the two step limits must be finite integers >= 1 (documented
-    deviation: the reference's commented-out ``float("inf")`` is refused -- the kernels size their scratch by it)."""
+    deviation: the reference's commented-out ``float("inf")`` is refused -- the kernels size their scratch by it).  The
+    optional key ``'kernel'`` is one of ``KERNEL_CHOICES``."""
     if args_DC3 is None:
         raise NotImplementedError("method 'DC3' needs args_DC3 (a dict with " + ", ".join(ARG_KEYS) + ")")
     missing = [key for key in ARG_KEYS if key not in args_DC3]
@@ -32,6 +34,13 @@ def check_args(args_DC3):
                 raise ValueError(f"args_DC3['{key}'] must be a finite integer >= 1, got {value!r}")
         if int(value) < 1:
             raise ValueError(f"args_DC3['{key}'] must be a finite integer >= 1, got {value!r}")
+    if "kernel" in args_DC3 and args_DC3["kernel"] not in KERNEL_CHOICES:
+        raise ValueError(f"args_DC3['kernel'] must be one of {KERNEL_CHOICES}, got {args_DC3['kernel']!r}")
+
+
+def kernel_choice(args_DC3):
+    """``'lane'``, ``'tile'`` or ``'auto'``: what ``args_DC3`` asks for."""
+    return (args_DC3 or {}).get("kernel", "lane")
 
 
 def setup(module, cs):

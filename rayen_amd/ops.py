@@ -489,8 +489,13 @@ def _workspace(pack, t, backward, max_steps=None, tile=False):
     call time)."""
     B, f64 = t.shape[0], int(t.dtype == torch.float64)
     if max_steps is not None:
-        name, limit, extra = "rayen_dc3_workspace_bytes", DC3_MAX_WORKSPACE_BYTES, 0
-        nbytes = int(_entry(name)(pack.handle, B, int(max_steps), f64, int(backward)))
+        limit, extra = DC3_MAX_WORKSPACE_BYTES, 0
+        if tile:
+            name = "rayen_dc3_tile_workspace_bytes"
+            nbytes = int(_entry(name)(pack.handle, B, int(max_steps), int(backward)))
+        else:
+            name = "rayen_dc3_workspace_bytes"
+            nbytes = int(_entry(name)(pack.handle, B, int(max_steps), f64, int(backward)))
     else:
         limit, extra = PROJ_MAX_WORKSPACE_BYTES, B * pack.m * t.element_size()   # (v*)
         if tile:
@@ -613,7 +618,9 @@ DC3_MAX_WORKSPACE_BYTES = 8 << 30
 
 class Dc3Pack(_SidePack):
     """Owner of one ``RayenDc3Pack*``: fp32 and fp64 images of the effective forms (``rayen_amd/dc3.py::pack_arrays``) on one
-    device, plus the NaN flag its forward raises."""
+    device, plus the NaN flag its forward raises.  The tile kernels' image (rayen_dc3_tile.hip) is uploaded on the first
+    call that asks for ``kernel='tile'``: a user who never does allocates nothing for it on the device.  Until then the
+    pack keeps a reference to the host arrays it was built from (no copy; released once the image is up)."""
     _layer = "dc3"
 
     def __init__(self, arrays, device_index):
@@ -624,11 +631,44 @@ class Dc3Pack(_SidePack):
                      ptr(a["re"]), int(a["Pe"].shape[0]), ptr(a["C"]), ptr(a["c0"]), ptr(a["partial"]), ptr(a["other"]),
                      self.n, self.k)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+        self._arrays = arrays      # the host arrays: what rayen_dc3_tile_pack_set reads, should it ever be called
+        self._tile_set = False
+        self._lane_served = {}
+
+    def tile_images(self):
+        """Upload the tile kernels' image (once; not while a stream is capturing)."""
+        if not self._tile_set:
+            a, ptr = self._arrays, _host_ptr
+            with torch.cuda.device(self.device_index):
+                _lib.check(_entry("rayen_dc3_tile_pack_set")(self.handle, ptr(a["A1e"]), ptr(a["b1e"]), ptr(a["Pe"]),
+                                                             ptr(a["qe"]), ptr(a["re"]), ptr(a["C"]), ptr(a["c0"])),
+                           "rayen_dc3_tile_pack_set")
+            self._tile_set = True
+            self._arrays = None
 
 
-def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
-    """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*``; ``steps`` is the batch-global number of steps."""
+DC3_KERNELS = ("lane", "tile")
+
+
+def _dc3_entry(direction, kernel, dtype, pack):
+    """The library entry of ``kernel``: ``'lane'`` is rayen_dc3.hip (one lane per row, the image in LDS), ``'tile'``
+    rayen_dc3_tile.hip (32 rows per workgroup on the matrix cores; fp32 only: an fp64 call is refused with
+    ``E_UNSUPPORTED``)."""
+    if kernel not in DC3_KERNELS:
+        raise ValueError(f"kernel must be one of {DC3_KERNELS}, got {kernel!r}")
+    if kernel == "lane":
+        return _typed(f"rayen_dc3_{direction}", dtype)
+    if dtype != torch.float32:
+        raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_dc3_tile_{direction}")
+    pack.tile_images()
+    return _entry(f"rayen_dc3_tile_{direction}_f32")
+
+
+def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps, kernel='lane'):
+    """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*`` (``kernel='tile'``: ``rayen_dc3_tile_forward_f32``);
+    ``steps`` is the batch-global number of steps."""
     _check_rows(q, pack.n, pack, "q", "dc3")
+    entry = _dc3_entry("forward", kernel, q.dtype, pack)
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
     if pack.inequalities == 0:
@@ -638,30 +678,55 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps):
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     steps = torch.empty((1,), dtype=torch.int32, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, False, max_steps)
-        code = _typed("rayen_dc3_forward", q.dtype)(
+        ws, nbytes = _workspace(pack, q, False, max_steps, tile=kernel == "tile")
+        code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(y), pack.k, float(lr), float(momentum),
             float(eps), int(max_steps), _ptr(steps), _ptr(ws), nbytes, _ptr(pack.nan_flag), _stream(q.device.index))
     _lib.check(code, "rayen_dc3_forward")
     return y, steps
 
 
-def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps):
-    """``grad_q`` (same shape as ``q``; columns beyond ``n`` are zero) through ``rayen_dc3_backward_*``."""
+def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps, kernel='lane'):
+    """``grad_q`` (same shape as ``q``; columns beyond ``n`` are zero) through ``rayen_dc3_backward_*`` (``kernel='tile'``:
+    ``rayen_dc3_tile_backward_f32``); ``steps`` may come from either kernel's forward."""
     _check_rows(q, pack.n, pack, "q", "dc3")
+    entry = _dc3_entry("backward", kernel, q.dtype, pack)
     q = _dense_rows(q, pack.n)
     grad_y = grad_y.to(q.dtype).contiguous()
     B = q.shape[0]
     grad_q = torch.empty((B, q.shape[1]), dtype=q.dtype, device=q.device) if q.shape[1] == pack.n else \
         torch.zeros((B, q.shape[1]), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, True, max_steps)
-        code = _typed("rayen_dc3_backward", q.dtype)(
+        ws, nbytes = _workspace(pack, q, True, max_steps, tile=kernel == "tile")
+        code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(grad_y), pack.k, _ptr(grad_q),
             grad_q.stride(0) if B else pack.n, float(lr), float(momentum), int(max_steps), _ptr(steps), _ptr(ws), nbytes,
             _stream(q.device.index))
     _lib.check(code, "rayen_dc3_backward")
     return grad_q
+
+
+def dc3_lane_served(pack, dtype):
+    """Does the lane kernel (rayen_dc3.hip) stage this pack's image at ``dtype``?  Asked with an empty batch: no kernel is
+    launched.  The library answers ``E_UNSUPPORTED`` before it touches the device; where it serves the pack, the empty call
+    clears its few bytes of scratch and the step count (two ``hipMemsetAsync`` on the current stream).  Asked once per
+    pack and dtype (the answer is remembered on the pack): not to be asked first while a stream is capturing."""
+    if dtype not in pack._lane_served:
+        try:
+            dc3_forward_raw(torch.empty((0, pack.n), dtype=dtype, device=f"cuda:{pack.device_index}"), pack, 0.0, 0.0, 0.0, 1)
+            pack._lane_served[dtype] = True
+        except _lib.RayenError as err:
+            if err.code != _lib.E_UNSUPPORTED:
+                raise
+            pack._lane_served[dtype] = False
+    return pack._lane_served[dtype]
+
+
+def dc3_tile_served(pack):
+    """Does the tile kernel serve this pack (its envelope: ``dc3_tile_served()`` in rayen_dc3_tile_image.h)?  Uploads the
+    tile image on first use (an allocation and a copy: not while a stream is capturing)."""
+    pack.tile_images()
+    return bool(_entry("rayen_dc3_tile_served")(pack.handle))
 
 
 @torch.library.custom_op("rayen_amd::dc3_project", mutates_args=())
@@ -703,6 +768,41 @@ def _dc3_backward(ctx, grad_y, grad_steps):
 
 
 dc3_project.register_autograd(_dc3_backward, setup_context=_dc3_setup_context)
+
+
+@torch.library.custom_op("rayen_amd::dc3_project_tile", mutates_args=())
+def dc3_project_tile(q: torch.Tensor, pack_id: int, lr: float, momentum: float, eps: float,
+                     max_steps: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``dc3_project`` on the tile kernel (rayen_dc3_tile.hip)."""
+    return dc3_forward_raw(q, _pack(pack_id), lr, momentum, eps, max_steps, kernel="tile")
+
+
+@dc3_project_tile.register_fake
+def _(q, pack_id, lr, momentum, eps, max_steps):
+    pack = _pack(pack_id)
+    return q.new_empty((q.shape[0], pack.k)), q.new_empty((1,), dtype=torch.int32)
+
+
+@torch.library.custom_op("rayen_amd::dc3_project_tile_bwd", mutates_args=())
+def dc3_project_tile_bwd(q: torch.Tensor, steps: torch.Tensor, grad_y: torch.Tensor, pack_id: int, lr: float,
+                         momentum: float, max_steps: int) -> torch.Tensor:
+    return dc3_backward_raw(q, steps, grad_y, _pack(pack_id), lr, momentum, max_steps, kernel="tile")
+
+
+@dc3_project_tile_bwd.register_fake
+def _(q, steps, grad_y, pack_id, lr, momentum, max_steps):
+    return torch.empty_like(q)
+
+
+def _dc3_tile_backward(ctx, grad_y, grad_steps):
+    q, steps = ctx.saved_tensors
+    if grad_y is None:
+        return None, None, None, None, None, None
+    return (torch.ops.rayen_amd.dc3_project_tile_bwd(q, steps, grad_y, ctx.pack_id, ctx.lr, ctx.momentum, ctx.max_steps),
+            None, None, None, None, None)
+
+
+dc3_project_tile.register_autograd(_dc3_tile_backward, setup_context=_dc3_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------
