@@ -514,6 +514,10 @@ int rayen_soft_cost_f32(const RayenCostPack* pack, const float* y, int64_t B, in
 int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, int64_t ld, double* cost, double* worst,
                         int32_t* which, double* grad, int64_t ld_grad, void* stream);
 
+/* ---- The same outputs for sets whose stacked rows do not fit LDS: the image streamed through LDS in windows (additive to
+ * ABI v15) */
+#include "rayen_hip_cost_stream.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,10 @@ EXPORTS_TILE = ("rayen_proj_tile_layout", "rayen_proj_tile_served", "rayen_proj_
 # tests/test_dc3_tile_host.py holds the two against each other
 EXPORTS_DC3_TILE = ("rayen_dc3_tile_shape_served", "rayen_dc3_tile_pack_set", "rayen_dc3_tile_served",
                     "rayen_dc3_tile_workspace_bytes", "rayen_dc3_tile_forward_f32", "rayen_dc3_tile_backward_f32")
+# additive to ABI v15, declared in include/rayen_hip_cost_stream.h (which rayen_hip.h includes, like the two above);
+# tests/test_cost_stream_host.py holds the two against each other
+EXPORTS_COST_STREAM = ("rayen_cost_stream_set", "rayen_cost_stream_served", "rayen_soft_cost_stream_f32",
+                       "rayen_soft_cost_stream_f64")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
 
@@ -225,9 +229,13 @@ def load():
     lib.rayen_cost_pack_destroy.argtypes = [p]
     lib.rayen_cost_served.restype = ctypes.c_int
     lib.rayen_cost_served.argtypes = [p, i32]
-    for name in ("rayen_soft_cost_f32", "rayen_soft_cost_f64"):
+    for name in ("rayen_soft_cost_f32", "rayen_soft_cost_f64", "rayen_soft_cost_stream_f32", "rayen_soft_cost_stream_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, i64, p, p, i32p, p, i64, p]
+    lib.rayen_cost_stream_set.restype = ctypes.c_int
+    lib.rayen_cost_stream_set.argtypes = [p, i64]
+    lib.rayen_cost_stream_served.restype = ctypes.c_int
+    lib.rayen_cost_stream_served.argtypes = [p, i32]
     if lib.rayen_abi_version() != ABI_VERSION:
         raise RuntimeError(f"librayen_hip.so ABI {lib.rayen_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

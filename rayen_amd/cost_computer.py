@@ -28,14 +28,21 @@ def _quad(y, P, q, r):
 
 
 class CostComputer(nn.Module):
-    def __init__(self, cs, fused=False):
+    def __init__(self, cs, fused=False, kernel="resident"):
         """``fused=True``: ``getSumSoftCostAllSamples`` is ``rayen_amd.soft_cost.SoftCost`` summed -- on a HIP device loss and
-        gradient in one launch of ``rayen_cost.hip`` -- instead of the chain of torch ops below; everything else is unchanged."""
+        gradient in one launch of ``rayen_cost.hip`` -- instead of the chain of torch ops below; everything else is unchanged.
+        ``kernel`` is ``SoftCost``'s (``'resident'``, ``'stream'``, ``'auto'``) and needs ``fused=True`` for any other value
+        than the default."""
         super().__init__()
         self.fused = bool(fused)
+        from .soft_cost import KERNELS
+        if kernel not in KERNELS:
+            raise ValueError(f"rayen_amd: CostComputer(kernel=...) must be one of {KERNELS}, got {kernel!r}")
+        if kernel != "resident" and not self.fused:
+            raise ValueError("rayen_amd: CostComputer(kernel=...) selects a route of the fused soft cost: pass fused=True")
         if self.fused:
             from .soft_cost import SoftCost
-            self.soft_cost = SoftCost(cs)
+            self.soft_cost = SoftCost(cs, kernel=kernel)
         if cs.has_quadratic_constraints:
             all_P, all_q, all_r = utils.getAllPqrFromQcs(cs.qcs)
             self.register_buffer("all_P", torch.Tensor(np.array(all_P)))

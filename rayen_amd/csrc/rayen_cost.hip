@@ -21,6 +21,10 @@
 // fp64: a lane per sample over the same image in natural order (LDS, broadcast reads); cones and quadratics take a second
 // pass over their rows for the gradient instead of holding the products.
 //
+// The walks over the image (the bodies of the two kernels' loops over tiles / items) are stated a second time in
+// rayen_cost_walk.h for the streamed route (rayen_cost_stream.hip), which must agree with these kernels bit for bit
+// (tests/test_gpu_soft_cost_stream.py): a change to the arithmetic here is a change there.
+//
 // Bounds: a lane whose sample is >= B reads nothing (its y is 0) and writes nothing; columns >= k are never touched in
 // y / grad (ld > k is skipped over); every LDS offset comes from the tile table the host built with the image.
 #include <hip/hip_runtime.h>
@@ -31,8 +35,7 @@
 #include <new>
 #include <vector>
 
-#include "rayen_cost_lmi.h"
-#include "rayen_side_pack.h"
+#include "rayen_cost_pack.h"
 
 namespace {
 
@@ -44,28 +47,6 @@ constexpr int kThreads = 256;                  // four waves: one per SIMD (the 
 using rayen::kLdsBudget;
 constexpr int kMinK64 = 8, kMaxK64 = 64;       // the fp64 kernel's K: k padded to a power of two between these
 constexpr int kDescWords = 8;                  // per tile / item: type, nvalid | row0, id0, form, fconst, ntiles | nrows, -, -
-
-}  // namespace
-
-struct RayenCostPack {
-  int device = -1, k = 0, n_simd = 1024;
-  // fp32 image (one buffer of 4-byte words): W [nt][32][64] swizzled | rowc [nt][32] | colv [nf][64] | desc [nt][8]
-  int32_t* img32 = nullptr;
-  int nt = 0, rowc_off = 0, colv_off = 0, desc_off = 0;
-  size_t bytes32 = 0;
-  bool served32 = false;
-  // fp64 image (8-byte words): W [R][K] | rowc [R] | colv [nf][K] | fconst [ni] | desc [ni][8] (ints)
-  double* img64 = nullptr;
-  int K64 = 0, ni = 0, rowc64_off = 0, colv64_off = 0, fc64_off = 0, desc64_off = 0;
-  size_t bytes64 = 0;
-  bool served64 = false;
-  // the set's LMI (rayen_cost_pack_set_lmi; rayen_cost_lmi.hip).  n_rows: the rows the images above hold; lmi_id: the
-  // LMI's index in the stacked order; eq_shift: what the equality rows' indices move up by (1 with an LMI, 0 without)
-  rayen::CostLmiImage* lmi = nullptr;
-  int n_rows = 0, lmi_id = 0, eq_shift = 0;
-};
-
-namespace {
 
 // row of a 32-row tile that register r of lane half h holds (C/D map of the 32x32 MFMA), also the k index of MFMA step r
 __host__ __device__ __forceinline__ int rho(const int r, const int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -409,11 +390,7 @@ __global__ __launch_bounds__(kThreads) void cost_lane64_kernel(const uint4* __re
 }
 
 // ---- host: the images
-struct SetView {
-  const double *A1, *b1, *P, *q, *r, *M, *s, *c, *d, *A2, *b2;
-  const int32_t* soc_rows;
-  int m1, nq, nsoc, m2, k;
-};
+using SetView = rayen::CostSetView;
 
 int float_bits(const float f) {
   int b;
@@ -421,8 +398,10 @@ int float_bits(const float f) {
   return b;
 }
 
+}  // namespace
+
 // fp32 image: tiles of 32 rows x 64 columns, 16-byte pieces XORed with the row (piece_slot)
-bool build32(const SetView& v, RayenCostPack* p, std::vector<int32_t>* words) {
+bool rayen::cost_build32(const SetView& v, RayenCostPack* p, std::vector<int32_t>* words, const size_t budget) {
   for (int j = 0; j < v.nsoc; ++j)
     if (v.soc_rows[j] > 64) return false;          // a cone's products are held in two tiles
   const int tl = (v.m1 + 31) / 32, te = (v.m2 + 31) / 32;
@@ -431,12 +410,12 @@ bool build32(const SetView& v, RayenCostPack* p, std::vector<int32_t>* words) {
   const int nt = tl + 2 * v.nq + tsoc + te, nf = v.nq + v.nsoc;
   const size_t n_words = (size_t)nt * 2048 + (size_t)nt * 32 + (size_t)nf * 64 + (size_t)nt * kDescWords;
   const size_t bytes = (n_words * 4 + 15) & ~(size_t)15;
+  p->bytes32 = bytes;
+  if (bytes > budget) return false;
   p->nt = nt;
   p->rowc_off = nt * 2048;
   p->colv_off = p->rowc_off + nt * 32;
   p->desc_off = p->colv_off + nf * 64;
-  p->bytes32 = bytes;
-  if (bytes > kLdsBudget) return false;
   std::vector<float> f(bytes / 4, 0.0f);
   std::vector<int32_t>& w = *words;
   w.assign(bytes / 4, 0);
@@ -488,22 +467,24 @@ bool build32(const SetView& v, RayenCostPack* p, std::vector<int32_t>* words) {
   return t == nt;
 }
 
-bool build64(const SetView& v, RayenCostPack* p, std::vector<double>* words) {
+bool rayen::cost_build64(const SetView& v, RayenCostPack* p, std::vector<double>* words, const size_t budget) {
   const int K = rayen::padded_width<kMinK64, kMaxK64>(v.k);
-  int msoc = 0;
+  int64_t msoc = 0;
   for (int j = 0; j < v.nsoc; ++j) msoc += v.soc_rows[j];
-  const int R = v.m1 + v.nq * v.k + msoc + v.m2, nf = v.nq + v.nsoc;
+  const int64_t R64 = (int64_t)v.m1 + (int64_t)v.nq * v.k + msoc + v.m2;
+  const int nf = v.nq + v.nsoc;
   const int ni = (v.m1 > 0) + v.nq + v.nsoc + (v.m2 > 0);
+  const size_t n_words = (size_t)R64 * K + (size_t)R64 + (size_t)nf * K + (size_t)ni + (size_t)ni * kDescWords / 2;
+  const size_t bytes = (n_words * 8 + 15) & ~(size_t)15;
   p->K64 = K;
   p->ni = ni;
+  p->bytes64 = bytes;
+  if (bytes > budget) return false;
+  const int R = (int)R64;
   p->rowc64_off = R * K;
   p->colv64_off = p->rowc64_off + R;
   p->fc64_off = p->colv64_off + nf * K;
   p->desc64_off = p->fc64_off + ni;
-  const size_t n_words = (size_t)p->desc64_off + (size_t)ni * kDescWords / 2;
-  const size_t bytes = (n_words * 8 + 15) & ~(size_t)15;
-  p->bytes64 = bytes;
-  if (bytes > kLdsBudget) return false;
   std::vector<double>& w = *words;
   w.assign(bytes / 8, 0.0);
   int32_t* desc = reinterpret_cast<int32_t*>(w.data() + p->desc64_off);
@@ -544,11 +525,7 @@ bool build64(const SetView& v, RayenCostPack* p, std::vector<double>* words) {
   return row == R && it == ni;
 }
 
-int check_call(const RayenCostPack* p, const void* y, const int64_t B, const int64_t ld, const void* grad, const int64_t ldg) {
-  if (p == nullptr || B < 0) return RAYEN_E_BAD_ARG;
-  if (B > 0 && (y == nullptr || ld < p->k || (grad != nullptr && ldg < p->k))) return RAYEN_E_BAD_ARG;
-  return RAYEN_OK;
-}
+namespace {
 
 template <bool GRAD>
 int launch32(const RayenCostPack* p, const float* y, int64_t B, int64_t ld, float* cost, float* worst, int32_t* which,
@@ -610,11 +587,26 @@ int rayen_cost_pack_create(const double* A1, const double* b1, int32_t m1, const
   p->n_rows = m1 + nq + nsoc + m2;
   p->lmi_id = m1 + nq + nsoc;
   if (k <= 64 && p->n_rows > 0) {     // k beyond: the pack exists and a call on its rows answers RAYEN_E_UNSUPPORTED
+    // the arrays, kept on the host in this order for the streamed route (rayen_cost_stream.hip: cost_stream_view)
+    const size_t kk = (size_t)k;
+    size_t msoc = 0;
+    for (int j = 0; j < nsoc; ++j) msoc += (size_t)soc_rows[j];
+    const double* src[11] = {A1, b1, P, q, r, M, s, c, d, A2, b2};
+    const size_t len[11] = {m1 * kk, (size_t)m1, nq * kk * kk, nq * kk, (size_t)nq, msoc * kk, msoc, nsoc * kk, (size_t)nsoc,
+                            m2 * kk, (size_t)m2};
+    try {
+      for (int a = 0; a < 11; ++a) p->host.insert(p->host.end(), src[a], src[a] + len[a]);
+      p->host_soc_rows.assign(soc_rows, soc_rows + nsoc);
+    } catch (const std::bad_alloc&) {
+      delete p;
+      return RAYEN_E_ALLOC;
+    }
+    p->m1 = m1; p->nq = nq; p->nsoc = nsoc; p->m2 = m2;
     const SetView v{A1, b1, P, q, r, M, s, c, d, A2, b2, soc_rows, m1, nq, nsoc, m2, k};
     std::vector<int32_t> w32;
     std::vector<double> w64;
-    p->served32 = build32(v, p, &w32);
-    p->served64 = build64(v, p, &w64);
+    p->served32 = rayen::cost_build32(v, p, &w32, kLdsBudget);
+    p->served64 = rayen::cost_build64(v, p, &w64, kLdsBudget);
     if ((p->served32 && !rayen::upload_image(w32, &p->img32)) || (p->served64 && !rayen::upload_image(w64, &p->img64))) {
       rayen_cost_pack_destroy(p);
       return RAYEN_E_ALLOC;
@@ -631,6 +623,7 @@ void rayen_cost_pack_destroy(RayenCostPack* p) {
     if (p->img32) (void)hipFree(p->img32);
     if (p->img64) (void)hipFree(p->img64);
     rayen::cost_lmi_free(p->lmi);
+    rayen::cost_stream_free(p->stream);
   }
   delete p;
 }
@@ -648,33 +641,17 @@ int rayen_cost_pack_set_lmi(RayenCostPack* pack, const double* F, int32_t r) {
 
 namespace {
 
-// the whole set at one precision: its rows (when it has any) and its LMI (when it has one)
+// (the resident route serves the rows whose whole image fits LDS)
 template <typename T>
 bool serves_set(const RayenCostPack* p) {
-  const bool rows = sizeof(T) == 8 ? p->served64 : p->served32;
-  if (p->n_rows > 0 && !rows) return false;
-  if (p->lmi != nullptr) return rayen::cost_lmi_serves<T>(p->lmi);
-  return p->n_rows > 0;
+  return rayen::cost_serves_set<T>(p, sizeof(T) == 8 ? p->served64 : p->served32);
 }
 
-// the rows' launch, then the LMI's on the same stream (accumulating when the rows came first)
 template <typename T, typename Rows>
 int soft_cost(const RayenCostPack* pack, const T* y, int64_t B, int64_t ld, T* cost, T* worst, int32_t* which, T* grad,
               int64_t ld_grad, void* stream, Rows&& launch_rows) {
-  int rc = check_call(pack, y, B, ld, grad, ld_grad);
-  if (rc != RAYEN_OK) return rc;
-  if (!serves_set<T>(pack)) return RAYEN_E_UNSUPPORTED;
-  const bool both = pack->lmi != nullptr && pack->n_rows > 0;
-  if (both && which != nullptr && worst == nullptr) return RAYEN_E_BAD_ARG;     // (the LMI's launch compares with the stored worst)
-  rc = rayen::check_device(pack->device);
-  if (rc != RAYEN_OK || B == 0) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (pack->n_rows > 0) {
-    rc = launch_rows(st);
-    if (rc != RAYEN_OK) return rc;
-  }
-  if (pack->lmi == nullptr) return RAYEN_OK;
-  return rayen::cost_lmi_launch<T>(pack->lmi, y, B, ld, cost, worst, which, grad, ld_grad, both ? 1 : 0, pack->lmi_id, st);
+  return rayen::cost_call<T>(pack, pack != nullptr && (sizeof(T) == 8 ? pack->served64 : pack->served32), y, B, ld, cost,
+                             worst, which, grad, ld_grad, stream, launch_rows);
 }
 
 }  // namespace

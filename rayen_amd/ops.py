@@ -1007,11 +1007,34 @@ class CostPack(_SidePack):
     def served(self, dtype):
         return bool(_entry("rayen_cost_served")(self.handle, int(dtype == torch.float64)))
 
+    def stream_served(self, dtype, window_bytes=0):
+        """Does the streamed route (``rayen_cost_stream.hip``: the stacked rows through LDS in windows of ``window_bytes``
+        bytes, 0 = the default of 80 KiB) serve the set at ``dtype``?  The first call, and every call with another window
+        size, builds and uploads the stream images; a pack nobody asks holds none."""
+        with torch.cuda.device(self.device_index):
+            _lib.check(_entry("rayen_cost_stream_set")(self.handle, int(window_bytes)), "rayen_cost_stream_set")
+        self._stream_set = True
+        return bool(_entry("rayen_cost_stream_served")(self.handle, int(dtype == torch.float64)))
 
-def soft_cost_raw(y, pack, want_grad):
-    """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``:
+
+COST_KERNELS = ("resident", "stream")
+
+
+def soft_cost_raw(y, pack, want_grad, kernel="resident"):
+    """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``
+    (``kernel='resident'``: the image of the stacked rows in LDS) or ``rayen_soft_cost_stream_*`` (``'stream'``: the image
+    through LDS in windows, at the window size of the pack's last ``stream_served`` call, the default if there was none):
     one launch (two for a set that has an LMI next to other constraints)."""
+    if kernel not in COST_KERNELS:
+        raise ValueError(f"rayen_amd: kernel must be one of {COST_KERNELS}, got {kernel!r}")
     _check_rows(y, pack.k, pack, "y", "cost")
+    name = "rayen_soft_cost"
+    if kernel == "stream":
+        name = "rayen_soft_cost_stream"
+        if not getattr(pack, "_stream_set", False):
+            with torch.cuda.device(pack.device_index):
+                _lib.check(_entry("rayen_cost_stream_set")(pack.handle, 0), "rayen_cost_stream_set")
+            pack._stream_set = True
     y = _dense_rows(y, pack.k)
     B = y.shape[0]
     cost = torch.empty((B,), dtype=y.dtype, device=y.device)
@@ -1019,10 +1042,10 @@ def soft_cost_raw(y, pack, want_grad):
     which = torch.empty((B,), dtype=torch.int32, device=y.device)
     grad = torch.empty((B, pack.k), dtype=y.dtype, device=y.device) if want_grad else None
     with _on_device(y.device):
-        code = _typed("rayen_soft_cost", y.dtype)(
+        code = _typed(name, y.dtype)(
             pack.handle, _ptr(y), B, y.stride(0) if B else pack.k, _ptr(cost), _ptr(worst), _ptr(which), _ptr(grad),
             pack.k, _stream(y.device.index))
-    _lib.check(code, "rayen_soft_cost")
+    _lib.check(code, name)
     return cost, worst, which, grad
 
 
@@ -1061,3 +1084,22 @@ def _cost_backward(ctx, grad_cost, grad_worst, grad_which, grad_grad):
 
 
 soft_cost.register_autograd(_cost_backward, setup_context=_cost_setup_context)
+
+
+@torch.library.custom_op("rayen_amd::soft_cost_stream", mutates_args=())
+def soft_cost_stream(y: torch.Tensor, pack_id: int, need_grad: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rayen_amd::soft_cost`` on the streamed route (``rayen_cost_stream.hip``): the same outputs, bit for bit where both
+    serve the set, and the same autograd."""
+    pack = _pack(pack_id)
+    cost, worst, which, grad = soft_cost_raw(y, pack, need_grad, kernel="stream")
+    return cost, worst, which, (grad if grad is not None else y.new_empty((0, pack.k)))
+
+
+@soft_cost_stream.register_fake
+def _(y, pack_id, need_grad):
+    B, k = y.shape[0], _pack(pack_id).k
+    return (y.new_empty((B,)), y.new_empty((B,)), y.new_empty((B,), dtype=torch.int32),
+            y.new_empty((B if need_grad else 0, k)))
+
+
+soft_cost_stream.register_autograd(_cost_backward, setup_context=_cost_setup_context)

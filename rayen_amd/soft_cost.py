@@ -19,6 +19,13 @@ one that adds to the first one's outputs otherwise.  The mirror below (the same 
 autograd; the LMI through ``torch.linalg.eigvalsh``) serves host tensors and sets the kernels refuse (one ``RuntimeWarning``;
 an error under ``RAYEN_STRICT_HIP=1``).  16-bit inputs are computed in fp32.  A row with a NaN answers ``cost = worst = NaN``,
 ``which = -1``; no other row is touched.
+
+``SoftCost(cs, kernel=...)`` chooses the route of device tensors.  ``'resident'`` (the default) is the above: the whole image
+of the stacked rows in LDS, refused beyond 160 KiB.  ``'stream'`` runs ``rayen_amd/csrc/rayen_cost_stream.hip`` through
+``rayen_amd::soft_cost_stream``: the same image cut into windows that a workgroup brings through LDS one after another, the
+same arithmetic in the same order (bit for bit the resident result where both serve), for sets of any number of rows
+(``k <= 64``).  ``'auto'`` takes the resident kernel wherever it serves at the input's dtype, else the streamed one, else the
+mirror.  Host tensors take the mirror under every value.
 """
 from __future__ import annotations
 
@@ -31,6 +38,7 @@ import torch.nn as nn
 
 from . import _lib
 
+KERNELS = ("resident", "stream", "auto")
 _NAMES = ("A1", "b1", "P", "q", "r", "M", "s", "c", "d", "A2", "b2", "F")
 
 
@@ -116,8 +124,11 @@ class SoftCost(nn.Module):
     """``forward(y) -> cost [B]`` (differentiable in ``y``), ``violation(y) -> (worst [B], which [B] int32)`` for
     ``y [B, k, 1]`` or ``[B, k]``."""
 
-    def __init__(self, cs):
+    def __init__(self, cs, kernel="resident"):
         super().__init__()
+        if kernel not in KERNELS:
+            raise ValueError(f"rayen_amd: SoftCost(kernel=...) must be one of {KERNELS}, got {kernel!r}")
+        self.kernel = kernel
         self.arrays = set_arrays(cs)           # fp64 numpy: what the packs are built from (picklable)
         self.k = int(cs.k)
         self.has_lmi_constraints = bool(cs.has_lmi_constraints)
@@ -130,6 +141,7 @@ class SoftCost(nn.Module):
         self.__dict__["_cost_packs"] = {}
         self.__dict__["_constants"] = {}
         self.__dict__["_unsupported"] = set()
+        self.__dict__["_routes"] = {}
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -138,7 +150,7 @@ class SoftCost(nn.Module):
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        state["_cost_packs"], state["_constants"], state["_unsupported"] = {}, {}, set()
+        state["_cost_packs"], state["_constants"], state["_unsupported"], state["_routes"] = {}, {}, set(), {}
         return state
 
     def cost_pack(self, device):
@@ -169,17 +181,32 @@ class SoftCost(nn.Module):
     def _mirror(self, y2):
         return mirror(self.constants(y2.dtype, y2.device), y2)
 
+    def _route(self, pack, dtype):
+        """``'resident'`` or ``'stream'``: the route ``kernel`` sends device rows of ``dtype`` to (sizes alone decide).
+        ``'auto'`` decides once per (device, dtype): the stream images are asked for at most once, at the default window."""
+        if self.kernel != "auto":
+            return self.kernel
+        key = (pack.device_index, dtype)
+        route = self._routes.get(key)
+        if route is None:
+            # (served by neither: 'resident', whose call refuses in the usual way)
+            route = "resident" if pack.served(dtype) or not pack.stream_served(dtype) else "stream"
+            self._routes[key] = route
+        return route
+
     def _evaluate(self, y2, want_grad):
         """``(cost, worst, which)`` of fp32 / fp64 rows: the kernel where it serves, the mirror elsewhere."""
-        if not y2.is_cuda or (y2.device.index, y2.dtype) in self._unsupported:
+        if not y2.is_cuda or (y2.device.index, y2.dtype, self.kernel) in self._unsupported:
             return self._mirror(y2)
         try:
             from . import ops
             pack, pack_id = self.cost_pack(y2.device)
+            route = self._route(pack, y2.dtype)
             if want_grad:
-                cost, worst, which, _ = torch.ops.rayen_amd.soft_cost(y2, pack_id, True)
+                op = torch.ops.rayen_amd.soft_cost_stream if route == "stream" else torch.ops.rayen_amd.soft_cost
+                cost, worst, which, _ = op(y2, pack_id, True)
             else:
-                cost, worst, which, _ = ops.soft_cost_raw(y2.detach(), pack, False)
+                cost, worst, which, _ = ops.soft_cost_raw(y2.detach(), pack, False, kernel=route)
             return cost, worst, which
         except _lib.RayenError as err:
             if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
@@ -187,7 +214,7 @@ class SoftCost(nn.Module):
             warnings.warn(f"rayen_amd: no HIP kernel serves this set's soft cost ({err}); this module now evaluates the "
                           "same formulas in torch ops (rayen_amd/soft_cost.py) on " + str(y2.device), RuntimeWarning,
                           stacklevel=4)
-            self._unsupported.add((y2.device.index, y2.dtype))
+            self._unsupported.add((y2.device.index, y2.dtype, self.kernel))
             return self._mirror(y2)
 
     def forward(self, y):
