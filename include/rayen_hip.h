@@ -357,6 +357,9 @@ int rayen_bar_backward_f32(const RayenBarPack* pack, const float* q, int64_t ldq
 int rayen_bar_backward_f64(const RayenBarPack* pack, const double* q, int64_t ldq, const double* rowstat,
                            const double* grad_y, int64_t B, double* grad_q, void* stream);
 
+/* (additive to ABI v15) the same layer with the image of G streamed through LDS in windows: five more entry points */
+#include "rayen_hip_bar_stream.h"
+
 /* ---- method='DC3' (ABI v10): the reference's completion + gradient-correction layer (rayen/constraint_module.py:265-336)
  *
  * With p = y[partial] (n values) and y[other] = c0 + C p (k - n values), T steps of

@@ -50,6 +50,10 @@ EXPORTS_DC3_TILE = ("rayen_dc3_tile_shape_served", "rayen_dc3_tile_pack_set", "r
 # tests/test_cost_stream_host.py holds the two against each other
 EXPORTS_COST_STREAM = ("rayen_cost_stream_set", "rayen_cost_stream_served", "rayen_soft_cost_stream_f32",
                        "rayen_soft_cost_stream_f64")
+# additive to ABI v15, declared in include/rayen_hip_bar_stream.h (which rayen_hip.h includes, like the three above);
+# tests/test_bar_stream_host.py holds the two against each other
+EXPORTS_BAR_STREAM = ("rayen_bar_resident_served", "rayen_bar_stream_forward_f32", "rayen_bar_stream_forward_f64",
+                      "rayen_bar_stream_backward_f32", "rayen_bar_stream_backward_f64")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 
 
@@ -171,6 +175,14 @@ def load():
     for name in ("rayen_bar_backward_f32", "rayen_bar_backward_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, p, p, i64, p, p]
+    lib.rayen_bar_resident_served.restype = ctypes.c_int
+    lib.rayen_bar_resident_served.argtypes = [p, ctypes.c_int32]
+    for name in ("rayen_bar_stream_forward_f32", "rayen_bar_stream_forward_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [p, p, i64, i64, p, i64, p, i32p, i64, p]
+    for name in ("rayen_bar_stream_backward_f32", "rayen_bar_stream_backward_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [p, p, i64, p, p, i64, p, i64, p]
     i32, f64 = ctypes.c_int32, ctypes.c_double
     lib.rayen_dc3_pack_create.restype = ctypes.c_int
     lib.rayen_dc3_pack_create.argtypes = [p, p, i32, p, p, p, i32, p, p, p, p, i32, i32, ctypes.POINTER(ctypes.c_void_p)]

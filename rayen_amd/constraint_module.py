@@ -18,7 +18,8 @@ constants with plain torch ops on the caller's device (``rayen_amd/eager.py``; t
 ``'RAYEN_old'`` (:460-466) runs on the same kernels; ``'UU'`` is the identity and kept because it
 is free; ``'Bar'`` (the barycentric baseline, :124-132 and :479-486) converts the linear part of the set to
 vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kernel per direction
-(``rayen_amd/csrc/rayen_bar.hip``); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
+(``rayen_amd/csrc/rayen_bar.hip``, or with the keyword ``bar_kernel='stream' | 'auto'`` ``rayen_bar_stream.hip``, which
+needs no LDS proportional to the number of generators); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
 quadratic sets only) needs ``args_DC3`` and runs its fixed iteration, batch-global stop included, on
 ``rayen_amd/csrc/rayen_dc3.hip`` or, with ``args_DC3['kernel'] = 'tile' | 'auto'``, ``rayen_dc3_tile.hip`` (host side:
 ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
@@ -64,10 +65,14 @@ class ConstraintModule(torch.nn.Module):
 
     def _route_key(self, old_head=False):
         """Third part of a refusal's key: the old head of RAYEN_old, the kernel ``args_DC3`` asks for (``False`` for the
-        default, ``'lane'``), ``False`` otherwise."""
+        default, ``'lane'``), the kernel ``bar_kernel`` asks for (``False`` for the default, ``'resident'``), ``False``
+        otherwise."""
         if self.method == 'DC3':
             kernel = _dc3.kernel_choice(self.args_DC3)
             return False if kernel == 'lane' else kernel
+        if self.method == 'Bar':
+            kernel = getattr(self, 'bar_kernel', 'resident')
+            return False if kernel == 'resident' else kernel
         return bool(old_head)
 
     def __setattr__(self, name, value):
@@ -75,10 +80,29 @@ class ConstraintModule(torch.nn.Module):
         if name == "mapper":
             self.__dict__["_fast"] = {}       # (the fast path caches "the mapper is the identity" per device and dtype)
 
-    def __init__(self, cs, input_dim=None, method='RAYEN', create_map=True, args_DC3=None):
+    BAR_KERNELS = ('resident', 'stream', 'auto')
+
+    def __init__(self, cs, input_dim=None, method='RAYEN', create_map=True, args_DC3=None, *, bar_kernel='resident',
+                 bar_window_bytes=0):
         super().__init__()
 
         self.method = method
+        if bar_kernel not in self.BAR_KERNELS:
+            raise ValueError(f"bar_kernel must be one of {self.BAR_KERNELS}, got {bar_kernel!r}")
+        if bar_kernel != 'resident' and method != 'Bar':
+            raise ValueError(f"bar_kernel={bar_kernel!r} chooses a kernel of method 'Bar'; this module's method is {method!r}")
+        if isinstance(bar_window_bytes, bool) or not isinstance(bar_window_bytes, int) or bar_window_bytes < 0 \
+                or bar_window_bytes % 16:
+            raise ValueError(f"bar_window_bytes must be 0 (the default window) or a positive multiple of 16, got {bar_window_bytes!r}")
+        if bar_window_bytes and bar_kernel == 'resident':
+            raise ValueError("bar_window_bytes is the window of the streamed kernels: it needs bar_kernel='stream' or 'auto'")
+        # method='Bar' on a HIP device: 'resident' (rayen_bar.hip, the image of G in LDS), 'stream' (rayen_bar_stream.hip, the
+        # image streamed through LDS in windows: no limit on the number of generators) or 'auto' (resident where it serves
+        # the pack at the input's dtype, else stream).  bar_window_bytes: the streamed kernels' window for tests and
+        # measurements, 0 = the default; the library refuses (RAYEN_E_BAD_ARG) one beyond the default or below one group of
+        # four generators at the pack's K.
+        self.bar_kernel = bar_kernel
+        self.bar_window_bytes = bar_window_bytes
         if method == 'Bar' and cs.has_quadratic_constraints:
             raise Exception(f"Method {method} cannot be used with quadratic constraints")     # (:24-25)
         if method == 'DC3':
@@ -264,6 +288,8 @@ class ConstraintModule(torch.nn.Module):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._fast = {}
+        self.__dict__.setdefault("bar_kernel", 'resident')       # (pickles from before the streamed Bar kernels)
+        self.__dict__.setdefault("bar_window_bytes", 0)
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
                                  'UU': self.forwardForUU, 'Bar': self.forwardForBar,
                                  'DC3': self.forwardForDC3}[self.method]
@@ -360,6 +386,14 @@ class ConstraintModule(torch.nn.Module):
         z = (self.V.to(q.dtype) @ lambdas if nv else 0) + (self.R.to(q.dtype) @ mus if nr else 0)
         return self.NA_E.to(q.dtype) @ z + self.yp.to(q.dtype)
 
+    def _bar_kernel_for(self, bp, dtype):
+        """The kernel a call at ``dtype`` runs.  ``'auto'``: the resident kernel wherever it serves the pack at ``dtype``,
+        else the streamed one (which serves every pack).  No timing enters the choice."""
+        kernel = self.bar_kernel
+        if kernel != 'auto':
+            return kernel
+        return 'resident' if bp.resident_served(dtype) else 'stream'
+
     def forwardForBar(self, q):
         if not q.is_cuda:
             return self._bar_reference(q)        # host tensors: the reference's formula, differentiable by autograd
@@ -370,8 +404,13 @@ class ConstraintModule(torch.nn.Module):
             return self._bar_reference(q2.unsqueeze(2))
         try:
             bp, pack_id = self.bar_pack(q2.device)
+            kernel = self._bar_kernel_for(bp, q2.dtype)
+            window = int(self.bar_window_bytes)
             if not (torch.is_grad_enabled() and q2.requires_grad) and not torch.compiler.is_compiling():
-                y, _ = ops.bar_forward_raw(q2, bp, want_rowstat=False)      # plain inference: straight to the C ABI
+                # plain inference: straight to the C ABI
+                y, _ = ops.bar_forward_raw(q2, bp, want_rowstat=False, kernel=kernel, window_bytes=window)
+            elif kernel == 'stream':
+                y, _ = torch.ops.rayen_amd.bar_project_stream(q2, pack_id, window)
             else:
                 y, _ = torch.ops.rayen_amd.bar_project(q2, pack_id)
         except _lib.RayenError as err:
@@ -379,7 +418,7 @@ class ConstraintModule(torch.nn.Module):
                 raise
             warnings.warn(f"rayen_amd: no HIP kernel serves this Bar layer ({err}); this module now runs the reference "
                           "formula with torch ops on " + str(q2.device), RuntimeWarning, stacklevel=3)
-            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, False))
+            self.__dict__.setdefault("_unsupported", set()).add((q2.device.index, q2.dtype, self._route_key()))
             return self._bar_reference(q2.unsqueeze(2))
         return y.unsqueeze(2)
 

@@ -532,40 +532,66 @@ class BarPack(_SidePack):
         yp = np.ascontiguousarray(np.reshape(yp, -1), dtype=np.float64)
         self._create(device_index, G.ctypes.data, yp.ctypes.data, self.k, self.nv, self.nr)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
+        # (asked once, here: a module's 'auto' route then looks the answer up, also while torch.compile traces it)
+        self._resident = {dtype: bool(_entry("rayen_bar_resident_served")(self.handle, int(dtype == torch.float64)))
+                          for dtype in (torch.float32, torch.float64)}
 
     @property
     def width(self):
         return self.nv + self.nr
 
+    def resident_served(self, dtype):
+        """Do ``rayen_bar_forward_*`` / ``rayen_bar_backward_*`` (the image of G resident in LDS) serve this pack at
+        ``dtype``?  (The streamed kernels serve every pack.)"""
+        return self._resident[dtype]
 
-def bar_forward_raw(q, pack, want_rowstat=True):
-    """``(y [B, k], rowstat [B] | None)`` through ``rayen_bar_forward_*``; ``rowstat`` is the per-row log-sum-exp of
-    the vertex logits (the backward's input)."""
+
+BAR_KERNELS = ("resident", "stream")
+
+
+def _bar_entry(kernel, direction, dtype):
+    """The typed entry point of a Bar call on ``kernel``."""
+    if kernel == "resident":
+        return _typed("rayen_bar_" + direction, dtype)
+    if kernel == "stream":
+        return _typed("rayen_bar_stream_" + direction, dtype)
+    raise ValueError(f"rayen_amd: kernel must be one of {BAR_KERNELS}, got {kernel!r}")
+
+
+def bar_forward_raw(q, pack, want_rowstat=True, kernel='resident', window_bytes=0):
+    """``(y [B, k], rowstat [B] | None)`` through ``rayen_bar_forward_*`` (``kernel='resident'``: the image of G in LDS) or
+    ``rayen_bar_stream_forward_*`` (``kernel='stream'``: the image streamed through LDS in windows of ``window_bytes``, 0 =
+    the default; the same bits wherever both serve the pack); ``rowstat`` is the per-row log-sum-exp of the vertex logits
+    (the backward's input)."""
+    fn = _bar_entry(kernel, "forward", q.dtype)
     _check_rows(q, pack.width, pack, "q", "bar")
     q = _dense_rows(q, pack.width)
     B = q.shape[0]
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     rowstat = torch.empty((B,), dtype=q.dtype, device=q.device) if want_rowstat else None
+    extra = () if kernel == "resident" else (int(window_bytes),)
     with _on_device(q.device):
-        code = _typed("rayen_bar_forward", q.dtype)(
-            pack.handle, _ptr(q), B, q.stride(0) if B else pack.width, _ptr(y), pack.k, _ptr(rowstat),
-            _ptr(pack.nan_flag), _stream(q.device.index))
-    _lib.check(code, "rayen_bar_forward")
+        code = fn(pack.handle, _ptr(q), B, q.stride(0) if B else pack.width, _ptr(y), pack.k, _ptr(rowstat),
+                  _ptr(pack.nan_flag), *extra, _stream(q.device.index))
+    _lib.check(code, "rayen_bar_forward" if kernel == "resident" else "rayen_bar_stream_forward")
     return y, rowstat
 
 
-def bar_backward_raw(q, rowstat, grad_y, pack):
-    """``grad_q`` (same shape as ``q``; columns beyond ``nv + nr`` are zero) through ``rayen_bar_backward_*``."""
+def bar_backward_raw(q, rowstat, grad_y, pack, kernel='resident', window_bytes=0):
+    """``grad_q`` (same shape as ``q``; columns beyond ``nv + nr`` are zero) through ``rayen_bar_backward_*`` or, with
+    ``kernel='stream'``, ``rayen_bar_stream_backward_*``."""
+    fn = _bar_entry(kernel, "backward", q.dtype)
     _check_rows(q, pack.width, pack, "q", "bar")
     q = _dense_rows(q, pack.width).contiguous()
     grad_y = grad_y.to(q.dtype).contiguous()
     rowstat = rowstat.contiguous()
     B = q.shape[0]
     grad_q = torch.empty_like(q) if q.shape[1] == pack.width else torch.zeros_like(q)
+    extra = () if kernel == "resident" else (int(window_bytes),)
     with _on_device(q.device):
-        code = _typed("rayen_bar_backward", q.dtype)(
-            pack.handle, _ptr(q), q.shape[1], _ptr(rowstat), _ptr(grad_y), B, _ptr(grad_q), _stream(q.device.index))
-    _lib.check(code, "rayen_bar_backward")
+        code = fn(pack.handle, _ptr(q), q.shape[1], _ptr(rowstat), _ptr(grad_y), B, _ptr(grad_q), *extra,
+                  _stream(q.device.index))
+    _lib.check(code, "rayen_bar_backward" if kernel == "resident" else "rayen_bar_stream_backward")
     return grad_q
 
 
@@ -605,6 +631,46 @@ def _bar_backward(ctx, grad_y, grad_rowstat):
 
 
 bar_project.register_autograd(_bar_backward, setup_context=_bar_setup_context)
+
+
+# the same layer on the streamed kernels (rayen_bar_stream.hip); window_bytes = 0: the default window
+@torch.library.custom_op("rayen_amd::bar_project_stream", mutates_args=())
+def bar_project_stream(q: torch.Tensor, pack_id: int, window_bytes: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(y [B, k], rowstat [B])``: the Bar layer's forward on the streamed kernel, on torch's current stream."""
+    return bar_forward_raw(q, _pack(pack_id), kernel="stream", window_bytes=window_bytes)
+
+
+@bar_project_stream.register_fake
+def _(q, pack_id, window_bytes):
+    pack = _pack(pack_id)
+    return q.new_empty((q.shape[0], pack.k)), q.new_empty((q.shape[0],))
+
+
+@torch.library.custom_op("rayen_amd::bar_project_stream_bwd", mutates_args=())
+def bar_project_stream_bwd(q: torch.Tensor, rowstat: torch.Tensor, grad_y: torch.Tensor, pack_id: int,
+                           window_bytes: int) -> torch.Tensor:
+    return bar_backward_raw(q, rowstat, grad_y, _pack(pack_id), kernel="stream", window_bytes=window_bytes)
+
+
+@bar_project_stream_bwd.register_fake
+def _(q, rowstat, grad_y, pack_id, window_bytes):
+    return torch.empty_like(q)
+
+
+def _bar_stream_setup_context(ctx, inputs, output):
+    q, pack_id, window_bytes = inputs
+    ctx.pack_id, ctx.window_bytes = pack_id, window_bytes
+    ctx.save_for_backward(q, output[1])
+
+
+def _bar_stream_backward(ctx, grad_y, grad_rowstat):
+    q, rowstat = ctx.saved_tensors
+    if grad_y is None:
+        return None, None, None
+    return torch.ops.rayen_amd.bar_project_stream_bwd(q, rowstat, grad_y, ctx.pack_id, ctx.window_bytes), None, None
+
+
+bar_project_stream.register_autograd(_bar_stream_backward, setup_context=_bar_stream_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------
