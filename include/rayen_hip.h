@@ -158,7 +158,8 @@ enum {
                                  waves, the batch streamed through a shared B-operand image in LDS */
   RAYEN_KERNEL_PRODUCTS = 9,  /* wide sets (ABI v7): the epilogue over products T = v W_ext' of a library GEMM */
   RAYEN_KERNEL_PAIR_WL = 11,  /* f16 pairs, the image of W resident in LDS, four waves per SIMD on groups of 32 samples (round 6) */
-  RAYEN_KERNEL_LMI_BLOCK = 10 /* one workgroup per sample, the packed lower triangle in LDS (one LMI to ~280 x 280 + linear rows; round 5) */
+  RAYEN_KERNEL_LMI_BLOCK = 10, /* one workgroup per sample, the packed lower triangle in LDS (one LMI to ~280 x 280 + linear rows; round 5) */
+  RAYEN_KERNEL_WIDE_FUSED = 12 /* wide sets without the products matrix (rayen_hip_wide_fused.h): rayen_ray_project_wide_fused_f32 */
 };
 int rayen_last_forward_kernel(void);
 
@@ -520,6 +521,9 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 /* ---- The same outputs for sets whose stacked rows do not fit LDS: the image streamed through LDS in windows (additive to
  * ABI v15) */
 #include "rayen_hip_cost_stream.h"
+
+/* ---- Wide sets (n > 128) in one launch, without the products matrix of the ABI v7 route (additive to ABI v15) */
+#include "rayen_hip_wide_fused.h"
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,11 @@ EXPORTS_COST_STREAM = ("rayen_cost_stream_set", "rayen_cost_stream_served", "ray
 # tests/test_bar_stream_host.py holds the two against each other
 EXPORTS_BAR_STREAM = ("rayen_bar_resident_served", "rayen_bar_stream_forward_f32", "rayen_bar_stream_forward_f64",
                       "rayen_bar_stream_backward_f32", "rayen_bar_stream_backward_f64")
+# additive to ABI v15, declared in include/rayen_hip_wide_fused.h (which rayen_hip.h includes, like the four above);
+# tests/test_wide_fused_host.py holds the two against each other
+EXPORTS_WIDE_FUSED = ("rayen_wide_fused_served", "rayen_ray_project_wide_fused_f32")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
+KERNEL_WIDE_FUSED = 12
 
 
 class RayenSegment(ctypes.Structure):
@@ -127,7 +131,8 @@ def load():
     lib.rayen_pack_info.argtypes = [p, ctypes.POINTER(RayenPackInfo)]
     fwd = [p, p, i64, i64, p, i64, p, i32p, i32p, p]
     for name in ("rayen_ray_project_f32", "rayen_ray_project_f64", "rayen_ray_project_generic_f32",
-                 "rayen_ray_project_generic_f64", "rayen_ray_project_old_f32", "rayen_ray_project_old_f64"):
+                 "rayen_ray_project_generic_f64", "rayen_ray_project_old_f32", "rayen_ray_project_old_f64",
+                 "rayen_ray_project_wide_fused_f32"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = fwd
     for name in ("rayen_ray_project_from_products_f32", "rayen_ray_project_from_products_f64"):
@@ -136,6 +141,8 @@ def load():
     for name in ("rayen_ray_project_bwd_coefficients_f32", "rayen_ray_project_bwd_coefficients_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, p, i64, i64, p, i32p, p, i64, p, i64, p, p]
+    lib.rayen_wide_fused_served.restype = ctypes.c_int
+    lib.rayen_wide_fused_served.argtypes = [p, ctypes.c_int32]
     lib.rayen_products_rows.restype = ctypes.c_int64
     lib.rayen_products_rows.argtypes = [p]
     lib.rayen_products_served.restype = ctypes.c_int

@@ -65,14 +65,16 @@ class ConstraintModule(torch.nn.Module):
 
     def _route_key(self, old_head=False):
         """Third part of a refusal's key: the old head of RAYEN_old, the kernel ``args_DC3`` asks for (``False`` for the
-        default, ``'lane'``), the kernel ``bar_kernel`` asks for (``False`` for the default, ``'resident'``), ``False``
-        otherwise."""
+        default, ``'lane'``), the kernel ``bar_kernel`` asks for (``False`` for the default, ``'resident'``), the kernel
+        ``wide_kernel`` asks for under method 'RAYEN' (``False`` for the default, ``'products'``), ``False`` otherwise."""
         if self.method == 'DC3':
             kernel = _dc3.kernel_choice(self.args_DC3)
             return False if kernel == 'lane' else kernel
         if self.method == 'Bar':
             kernel = getattr(self, 'bar_kernel', 'resident')
             return False if kernel == 'resident' else kernel
+        if self.method == 'RAYEN' and getattr(self, 'wide_kernel', 'products') != 'products':
+            return self.wide_kernel          # (method 'RAYEN' has no old head)
         return bool(old_head)
 
     def __setattr__(self, name, value):
@@ -81,12 +83,23 @@ class ConstraintModule(torch.nn.Module):
             self.__dict__["_fast"] = {}       # (the fast path caches "the mapper is the identity" per device and dtype)
 
     BAR_KERNELS = ('resident', 'stream', 'auto')
+    WIDE_KERNELS = ops.WIDE_KERNELS
 
     def __init__(self, cs, input_dim=None, method='RAYEN', create_map=True, args_DC3=None, *, bar_kernel='resident',
-                 bar_window_bytes=0):
+                 bar_window_bytes=0, wide_kernel='products'):
         super().__init__()
 
         self.method = method
+        if wide_kernel not in self.WIDE_KERNELS:
+            raise ValueError(f"wide_kernel must be one of {self.WIDE_KERNELS}, got {wide_kernel!r}")
+        if wide_kernel != 'products' and method != 'RAYEN':
+            raise ValueError(f"wide_kernel={wide_kernel!r} chooses a kernel of method 'RAYEN'; this module's method is {method!r}")
+        # method='RAYEN' on wide sets (n beyond the register-resident kernels, ops._WIDE_MIN_N): 'products' (the default: a
+        # library GEMM and rayen_wide.hip over its products) or 'fused' (rayen_wide_fused.hip: one launch, no products
+        # matrix; fp32, no LMI, n <= 1024 -- anything else takes the module's loud path).  No effect on narrower sets.  The
+        # backward runs on the products route either way.  There is no 'auto': both serve the same sets, and no timing
+        # enters a dispatch here.
+        self.wide_kernel = wide_kernel
         if bar_kernel not in self.BAR_KERNELS:
             raise ValueError(f"bar_kernel must be one of {self.BAR_KERNELS}, got {bar_kernel!r}")
         if bar_kernel != 'resident' and method != 'Bar':
@@ -290,6 +303,7 @@ class ConstraintModule(torch.nn.Module):
         self._fast = {}
         self.__dict__.setdefault("bar_kernel", 'resident')       # (pickles from before the streamed Bar kernels)
         self.__dict__.setdefault("bar_window_bytes", 0)
+        self.__dict__.setdefault("wide_kernel", 'products')      # (pickles from before the fused wide forward)
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
                                  'UU': self.forwardForUU, 'Bar': self.forwardForBar,
                                  'DC3': self.forwardForDC3}[self.method]
@@ -310,12 +324,17 @@ class ConstraintModule(torch.nn.Module):
         try:
             dp, pack_id = self.device_pack(v.device)
             need_active = torch.is_grad_enabled() and v.requires_grad
+            fused = not old_head and getattr(self, "wide_kernel", 'products') == 'fused'
             if not need_active and type(v) is torch.Tensor and not torch.compiler.is_compiling():
                 # plain inference call: straight to the C ABI (the same code the registered op runs; the dispatcher
                 # layers around a custom op cost ~10 us per call, as much as the kernel at small batches)
-                y, _, _ = ops.project_raw(v, dp, want_active=False, old_head=old_head, want_kappa=False)
+                y, _, _ = ops.project_raw(v, dp, want_active=False, old_head=old_head, want_kappa=False,
+                                          wide_kernel='fused' if fused else 'products')
                 return y, None
-            y, kappa, _ = torch.ops.rayen_amd.ray_project(v, pack_id, need_active, old_head)
+            if fused:
+                y, kappa, _ = torch.ops.rayen_amd.ray_project_wide_fused(v, pack_id, need_active)
+            else:
+                y, kappa, _ = torch.ops.rayen_amd.ray_project(v, pack_id, need_active, old_head)
             return y, kappa
         except _lib.RayenError as err:
             if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
@@ -325,7 +344,7 @@ class ConstraintModule(torch.nn.Module):
             # RAYEN_STRICT_HIP=1 turns it back into the error.
             warnings.warn(f"rayen_amd: no HIP kernel serves this constraint set ({err}); this module now runs the "
                           "packed torch evaluator (rayen_amd/eager.py) on " + str(v.device), RuntimeWarning, stacklevel=3)
-            self.__dict__.setdefault("_unsupported", set()).add((v.device.index, v.dtype, bool(old_head)))
+            self.__dict__.setdefault("_unsupported", set()).add((v.device.index, v.dtype, self._route_key(old_head)))
             return eager.project(self, v, old_head=old_head)
 
     def computeKappa(self, v_bar):
@@ -334,15 +353,16 @@ class ConstraintModule(torch.nn.Module):
         if not v.is_cuda or self._refused(v) or v.dtype not in (torch.float32, torch.float64):
             return eager.evaluator_for(self, v).kappa(v[:, :self.n]).reshape(-1, 1, 1)
         dp, _ = self.device_pack(v.device)
+        wide = self.wide_kernel if self.method == 'RAYEN' else 'products'
         try:
-            _, kappa, _ = ops.project_raw(v, dp, want_y=False, want_active=False)
+            _, kappa, _ = ops.project_raw(v, dp, want_y=False, want_active=False, wide_kernel=wide)
         except _lib.RayenError as err:
             if err.code != _lib.E_UNSUPPORTED:
                 raise
             # the kernels that always write y (an LMI on the workgroup-per-sample kernels, alone, next to quadratics / cones
             # or behind the products GEMM; rayen_abi.hip::mixed_forward) decline y == NULL: same kernels, a scratch y
             try:
-                _, kappa, _ = ops.project_raw(v, dp, want_y=True, want_active=False)
+                _, kappa, _ = ops.project_raw(v, dp, want_y=True, want_active=False, wide_kernel=wide)
             except _lib.RayenError as err2:
                 if err2.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
                     raise
@@ -545,7 +565,9 @@ class ConstraintModule(torch.nn.Module):
             entry = None
             if (self.method == 'RAYEN' and isinstance(self.mapper, nn.Sequential) and len(self.mapper) == 0
                     and not self._refused(x) and x.dtype in (torch.float32, torch.float64)
-                    and self.n < ops._WIDE_MIN_N[x.dtype]):      # (wide sets: GEMM + products epilogue, ops.project_raw)
+                    and self.n < ops._WIDE_MIN_N[x.dtype]      # (wide sets: GEMM + products epilogue, ops.project_raw)
+                    # (a set with an LMI may take the wide route earlier: wide_kernel='fused' gets its refusal there)
+                    and not (getattr(self, "wide_kernel", 'products') == 'fused' and self.cs.has_lmi_constraints)):
                 try:
                     dp, _ = self.device_pack(x.device)
                     fn = ops._entry(ops._FWD[(x.dtype, False)])

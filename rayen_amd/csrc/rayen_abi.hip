@@ -808,6 +808,7 @@ void rayen_pack_destroy(RayenPack* p) {
   if (p->pr32m) mfma_pair_free(p->pr32m);
   if (p->ws8_32) mfma_pair_ws8_free(p->ws8_32);
   if (p->wide) wide_free(p->wide);
+  if (p->wf32) wide_fused_free(p->wf32);
   if (p->q32) lmi_quad_free(p->q32);
   if (p->w32) lmi_wave_free(p->w32);
   if (p->w64) lmi_wave_free(p->w64);
@@ -895,6 +896,18 @@ int rayen_products_served(const RayenPack* p, int f64) {
   if (p->wide != nullptr) return 1;
   if (!lmi_products_pack(p)) return 0;
   return f64 ? lmi_block_products_serves<double>(p->w64) : lmi_block_products_serves<float>(p->w32);
+}
+
+int rayen_wide_fused_served(const RayenPack* p, int32_t f64) { return (p != nullptr && !f64 && wide_fused_served(p)) ? 1 : 0; }
+
+int rayen_ray_project_wide_fused_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy,
+                                     float* kappa, int32_t* active, int32_t* nan_flag, void* stream) {
+  if (p == nullptr || B < 0 || (B > 0 && v == nullptr) || ldv < p->n || (y != nullptr && ldy < p->k)) return RAYEN_E_BAD_ARG;
+  if (B > ((int64_t)1 << 31) - 32) return RAYEN_E_BAD_ARG;
+  const int rc = check_ready<float>(p, false);
+  if (rc) return rc;
+  g_last_forward = RAYEN_KERNEL_WIDE_FUSED;
+  return wide_fused_forward(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
 }
 
 static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy,

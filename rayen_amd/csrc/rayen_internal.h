@@ -63,11 +63,13 @@ struct SplitImage;      // rayen_mfma_split.hip
 struct PairImage;       // rayen_pair_image.h
 struct Ws8Image;        // rayen_mfma_pair_ws8.hip
 struct WideImage;       // rayen_wide.hip
+struct WideFusedImage;  // rayen_wide_fused.hip
 
 }  // namespace rayen
 
 // Immutable after rayen_pack_create returns (every device image is built there), so it is shared by threads and
-// streams without a lock.
+// streams without a lock -- but for `wf32`, the image of the opt-in fused wide forward, which its first call builds under
+// a lock of its own (rayen_wide_fused.hip).
 struct RayenPack {
   int device = -1;
   int k = 0, n = 0, n_rows = 0;
@@ -104,6 +106,10 @@ struct RayenPack {
   rayen::Ws8Image* ws8_32 = nullptr;   // the same image dealt out to eight W-stationary waves (null: not served)
   int pr32_state = 0;            // the same for the f16-pair kernel (which is preferred when both are accepted)
   rayen::WideImage* wide = nullptr;    // segment tables of the products epilogue (any n; packs without an LMI)
+  // the fused wide forward's image of W_ext: the ONE lazy member, built under rayen_wide_fused.hip's lock the first time that
+  // route is asked for (state 0: not asked yet | 1: built | 2: the route does not serve the pack)
+  mutable rayen::WideFusedImage* wf32 = nullptr;
+  mutable int wf32_state = 0;
   double check_split = -1.0, check_exact = -1.0, check_pair = -1.0;  // worst row errors against fp64 (fp32_selfcheck)
   // [linear rows, quadratics, cones] + ONE LMI the lane kernels do not hold: the lane kernel evaluates everything but the
   // LMI (generic image built with skip_lmi), the workgroup-per-sample kernel the LMI on top of that (rayen_abi.hip)
@@ -124,6 +130,12 @@ template <typename T>
 int wide_bwd_coefficients(const RayenPack* p, const WideImage* img, const T* Tm, int64_t ldt, const T* v, int64_t B,
                           int64_t ldv, const T* kappa, const int32_t* active, const T* gy, int64_t ldg, T* C, int64_t ldc,
                           T* gs, hipStream_t stream);
+
+// wide sets without the products matrix (rayen_wide_fused.hip): fp32, no LMI, n <= 1024, the tile and scratch within LDS
+bool wide_fused_served(const RayenPack* p);
+void wide_fused_free(WideFusedImage* img);
+int wide_fused_forward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy, float* kappa,
+                       int32_t* active, int32_t* nan_flag, hipStream_t stream);
 
 // SIMDs the persistent grids may fill: all of the device's minus rayen_reserve_cus() compute units (a collective that
 // runs beside the projection -- RCCL's all-gather kernels in the multi-GPU step -- needs CUs of its own)

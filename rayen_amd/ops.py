@@ -162,13 +162,22 @@ def _wide_route(v, pack, force_generic, old_head):
     return Wt
 
 
+WIDE_KERNELS = ('products', 'fused')
+
+
 def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old_head=False, out=None,
-                want_kappa=True):
+                want_kappa=True, wide_kernel='products'):
     """Direct call of the C ABI on an existing ``DevicePack``; returns (y|None, kappa|None, active|None).
 
     ``old_head``: the ``RAYEN_old`` step rule; ``v`` then carries ``beta`` in column ``n``.
     ``out``: a ``[B, >=k]`` tensor (unit column stride) whose first ``k`` columns receive ``y`` -- e.g. this
-    rank's rows of a gather buffer -- instead of a fresh allocation."""
+    rank's rows of a gather buffer -- instead of a fresh allocation.
+    ``wide_kernel``: what serves a call that takes the wide route (``_wide_route``): ``'products'`` -- the library GEMM and
+    the epilogue over its products -- or ``'fused'`` -- ``rayen_ray_project_wide_fused_f32`` (rayen_wide_fused.hip): one
+    launch, no GEMM and no products matrix; fp32, no LMI, n <= 1024, anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on
+    a call that does not take the wide route."""
+    if wide_kernel not in WIDE_KERNELS:
+        raise ValueError(f"wide_kernel must be one of {WIDE_KERNELS}, got {wide_kernel!r}")
     _check_input(v, pack)
     if old_head and v.shape[1] < pack.consts.n + 1:
         raise RuntimeError(f"rayen_amd: RAYEN_old needs {pack.consts.n + 1} input columns, got {v.shape[1]}")
@@ -186,6 +195,15 @@ def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old
     active = torch.empty((B, 2), dtype=torch.int32, device=v.device) if want_active else None
     Wt = _wide_route(v, pack, force_generic, old_head) if B else None
     with _on_device(v.device):
+        if Wt is not None and wide_kernel == 'fused':
+            if v.dtype != torch.float32:
+                code = _lib.E_UNSUPPORTED        # (the fused kernel is fp32 only: rayen_wide_fused_served(pack, 1) == 0)
+            else:
+                code = _entry("rayen_ray_project_wide_fused_f32")(
+                    pack.handle, _ptr(v), B, v.stride(0), _ptr(y), y.stride(0) if y is not None else k, _ptr(kappa),
+                    _ptr(active), _ptr(pack.nan_flag), _stream(v.device.index))
+            _lib.check(code, "rayen_ray_project_wide_fused")
+            return y, kappa, active
         if Wt is not None:
             n = pack.consts.n
             prods = torch.mm(v if v.shape[1] == n else v[:, :n], Wt)         # [B, rows of W_ext]: the library GEMM
@@ -215,6 +233,25 @@ def ray_project(v: torch.Tensor, pack_id: int, need_active: bool, old_head: bool
 
 @ray_project.register_fake
 def _(v, pack_id, need_active, old_head=False):
+    pack = _pack(pack_id)
+    B = v.shape[0]
+    return (v.new_empty((B, pack.consts.k)), v.new_empty((B,)),
+            v.new_empty((B if need_active else 0, 2), dtype=torch.int32))
+
+
+@torch.library.custom_op("rayen_amd::ray_project_wide_fused", mutates_args=())
+def ray_project_wide_fused(v: torch.Tensor, pack_id: int, need_active: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rayen_amd::ray_project`` with ``wide_kernel='fused'``: wide sets on rayen_wide_fused.hip (a call that does not take
+    the wide route runs what ``ray_project`` runs).  Its backward is ``ray_project``'s: the products route consumes this
+    forward's ``kappa`` and ``active``."""
+    y, kappa, active = project_raw(v, _pack(pack_id), want_active=need_active, wide_kernel='fused')
+    if active is None:
+        active = torch.empty((0, 2), dtype=torch.int32, device=v.device)
+    return y, kappa, active
+
+
+@ray_project_wide_fused.register_fake
+def _(v, pack_id, need_active):
     pack = _pack(pack_id)
     B = v.shape[0]
     return (v.new_empty((B, pack.consts.k)), v.new_empty((B,)),
@@ -337,6 +374,18 @@ def _backward(ctx, grad_y, grad_kappa, grad_active):
 
 
 ray_project.register_autograd(_backward, setup_context=_setup_context)
+
+
+def _wide_fused_setup_context(ctx, inputs, output):
+    v, pack_id, need_active = inputs
+    _setup_context(ctx, (v, pack_id, need_active, False), output)
+
+
+def _wide_fused_backward(ctx, grad_y, grad_kappa, grad_active):
+    return _backward(ctx, grad_y, grad_kappa, grad_active)[:3]
+
+
+ray_project_wide_fused.register_autograd(_wide_fused_backward, setup_context=_wide_fused_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------
