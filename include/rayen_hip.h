@@ -172,6 +172,18 @@ int rayen_last_forward_kernel(void);
  * value from the environment variable RAYEN_PAIR_IO.  mode outside 0..3 only queries.  Returns the previous setting. */
 int rayen_pair_schedule(int mode);
 
+/* Tuning / A-B switch (round 7, process-wide): screening in schedule 3 of the f16-pair forward.  kappa is a maximum over
+ * segments; in front of a quadratic / cone that owns its tiles the walk bounds the segment's candidate for the 32 samples
+ * of a group (spectral constant of the rows as laid out x ||v||^2, through the segment's own closer) and skips its tiles
+ * when the bound is below the running maximum of every live sample -- same y, kappa and record bit for bit
+ * (rayen_amd/csrc/rayen_mfma_pair_wl.hip, "Screening").  1 (default): on for calls without the fused mapper | 0: off, the
+ * instances of round 6.  Initial value from RAYEN_PAIR_SCREEN.  Any other mode only queries.  Returns the previous setting. */
+int rayen_pair_screen(int mode);
+/* Arm (device_counts: 64 x uint32 of device memory, zeroed by the caller) or disarm (NULL) the screening counters: while
+ * armed, every screening launch ADDS to device_counts[s] the number of 32-sample groups for which segment s was skipped
+ * (one atomic per wave at its exit).  Process-wide; the buffer must outlive the launches issued while it is armed. */
+int rayen_pair_screen_counters(uint32_t* device_counts);
+
 /* Multi-GPU step (ABI v4, process-wide): leave `cus` compute units out of the persistent grids of the projection
  * kernels, for a collective that runs beside them -- the all-gather of y that BASELINE.json's multi-GPU layout adds
  * (RCCL's kernels need CUs; a grid that fills every SIMD with resident waves serialises them behind the projection).

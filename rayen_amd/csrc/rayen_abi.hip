@@ -460,6 +460,16 @@ int rayen_pair_schedule(int mode) {
   return pair_schedule();
 }
 
+int rayen_pair_screen(int mode) {
+  if (mode == 0 || mode == 1) return pair_screen_cell().exchange(mode, std::memory_order_relaxed);
+  return pair_screen_cell().load(std::memory_order_relaxed);
+}
+
+int rayen_pair_screen_counters(uint32_t* device_counts) {
+  pair_screen_counters_cell().store(device_counts, std::memory_order_relaxed);
+  return RAYEN_OK;
+}
+
 const char* rayen_strerror(int code) {
   switch (code) {
     case RAYEN_OK: return "ok";

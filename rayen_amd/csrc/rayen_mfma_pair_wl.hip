@@ -25,6 +25,27 @@
 //     module's mapper in front (NKX > 0: its image next to W's).
 // The item list, the image, the epilogues and the order of the products inside a tile are the other schedules': same bits.
 //
+// Screening (round 7; SCREEN instances, rayen_pair_screen): kappa is a maximum over segments, so a quadratic / cone whose
+// candidate is below the running maximum for all 32 samples of a group changes neither kappa nor y nor the arg-max record,
+// and its tiles (config 3: 18 MFMAs and 16 A-operand reads per cone) need not be multiplied.  In front of the first item of
+// such a segment (side table WlScreen, rayen_pair_image.h: one record per item, loaded with the previous item's record) the
+// wave forms   ub = closer(aux rows, cnst * ||sv v||^2)   with the segment's OWN closer and skips the segment's items iff
+// ub < max(kap, other half's kap) on every live lane (dead lanes of a ragged group have no say; a NaN or an infinite row
+// makes every comparison false and skips nothing).  The segments behind it are decided at the same point until one stays;
+// then the A operands of the item that does run are fetched over the ones prefetched for the skipped item.
+//   Why ub dominates the candidate the walk would have computed.  The accumulators of the segment's items are
+// acc = (gW f_s R)(sv v) with R the rows as laid out, so their sum of squares is ||gW f_s R sv v||^2 <= lambda_max((gW f_s)^2
+// R'R) ||sv v||^2 in exact arithmetic; cnst is that eigenvalue (fp64 Jacobi, certified by a Cholesky of c I - R'R:
+// spectral_bound_rows) times 1 + 2^-10.  The margin pays for: the f16 pairs of W and of sv v (each 2^-22 of its row's
+// largest entry, the dropped p2 p2 products 2^-22 again), the fp32 accumulation of 64 products per accumulator and of the 64
+// squares (errors relative to ||R||_F ||v|| <= 8 sqrt(lambda_max) ||v||: below 2^-15 of the bound together), and the fp32
+// sum ||sv v||^2 computed here (2^-19): three orders of magnitude inside 2^-10.  Both closers are monotone in the sum of
+// squares operation by operation -- sqrt, products by positive constants and sums round monotonically; in
+// pair_soc_candidate (a' < 0, checked at image creation) cp, disc and root grow with it and the root taken,
+// (-bp - root) / 2a', grows with root and is the larger of the two -- and a candidate of 0 (negative discriminant, NaN)
+// never beats the running maximum.  So ub >= the candidate, and a skipped candidate would have lost every comparison:
+// same bits (tests/test_gpu_pair_wl_screen.py, and every bit-for-bit test of the four schedules).
+//
 // Served: NA_E = I, n = k in (32 (NKK - 1), 32 NKK] and a multiple of 4, rows 16-byte aligned, the image + the aux patches within 160 KiB of LDS, at most
 // sixteen aux rows at NKK = 2 (eight behind a mapper).  Everything else stays on the other schedules.
 #include "rayen_split_image.h"
@@ -51,7 +72,8 @@ namespace {
 constexpr int kWlWaves = RAYEN_WL_WAVES;      // waves per workgroup = per CU
 constexpr int kWlNT = RAYEN_WL_NT;            // sample tiles (of 32) per wave and group
 // developer ablation builds (scripts/ubench/tu_variant.sh rayen_mfma_pair_wl <name> -DRAYEN_WL_ABL=<bits>; WRONG RESULTS):
-// 1 rows requested once per wave | 2 no rows of y stored | 8 plain stores | 16 no epilogues | 32 no MFMAs
+// 1 rows requested once per wave | 2 no rows of y stored | 8 plain stores | 16 no epilogues | 32 no MFMAs | 64 the walk stops four
+// items early (config 3: both cones -- the ceiling of what screening them can give)
 #ifndef RAYEN_WL_ABL
 #define RAYEN_WL_ABL 0
 #endif
@@ -129,14 +151,16 @@ extern "C" int rayen_debug_wl_clock(void* dst, size_t bytes) {
 // rayen_mfma_pair.hip's mapped instances, bit for bit): `v` / `ldv` / `n_in` are then x, its leading dimension and its width, the
 // mapper's f16-pair image (NKK x 2 NKX K-steps x 2 pieces of 1 KiB, then bias, gM, 1 / gM: pair_mapper_image_kernel) is copied into
 // LDS behind the image of W, and v reaches memory only when v_out != null (training).
-template <int NKK, bool TRACK, int NT, int NW, int NKX = 0>
+template <int NKK, bool TRACK, int NT, int NW, int NKX = 0, bool SCREEN = false>
 __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     const f16x8* __restrict__ Wh, const MItem* __restrict__ items, int n_items,
     const MPack* __restrict__ packs, const float* __restrict__ y0, int n_tiles, int n,
     const float* __restrict__ v, int64_t B, int64_t ldv, float* __restrict__ y, int64_t ldy,
     float* __restrict__ kappa_out, int32_t* __restrict__ active_out,
     int32_t* __restrict__ nan_flag, const float w_scale, const float w_inv,
-    const f16x8* __restrict__ mimg, int n_in, float* __restrict__ v_out, int64_t ldvo) {
+    const f16x8* __restrict__ mimg, int n_in, float* __restrict__ v_out, int64_t ldvo,
+    const WlScreen* __restrict__ scr, unsigned* __restrict__ scr_count) {
+  static_assert(!SCREEN || (NT == 1 && NKX == 0), "screening: one sample tile per wave, no mapper in front");
   constexpr int NS = NKK * 2, NCH = NS * 2, NQ = NKK * 4, AUXR = WlGeom<NKK, (NKX > 0)>::AUXR;
   constexpr int NSX = NKX * 2, NQX = NKX * 4, MCH = NKK * NSX * 2;   // the mapper's K-steps, row pieces, 1-KiB chunks
   extern __shared__ __attribute__((aligned(1024))) char wl_smem[];
@@ -162,6 +186,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   int64_t grp = (int64_t)blockIdx.x + (int64_t)wave * grp_stride;
   bool bad = false;
   bool first_walk = true;
+  unsigned skipped = 0;      // (SCREEN) lane s: segment-groups of segment s this wave skipped
 #ifdef RAYEN_WL_STAMPS
   int stamp_round = 0;
   bool stamp_on = false;
@@ -472,6 +497,22 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
       }
       nan_row[t] = pair_nan_seen(z);
     }
+    // (SCREEN) ||sv v||^2 of the lane's row, from the SCALED values (a row of 1e-25 does not underflow to a bound of 0): two
+    // chains over the lane's half, the halves added
+    float nv2 = 0.f;
+    if constexpr (SCREEN) {
+      float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int c = 0; c < 4; c += 2) {
+          const float x0 = vraw[0][q][c] * v_scl[0], x1 = vraw[0][q][c + 1] * v_scl[0];
+          s0 = fmaf(x0, x0, s0);
+          s1 = fmaf(x1, x1, s1);
+        }
+      nv2 = s0 + s1;
+      nv2 += xhalf(nv2);
+    }
     __builtin_amdgcn_sched_barrier(0);
     // ---- the next group's rows: in flight for the whole walk
     if (RAYEN_WL_AHEAD && next < n_groups && !(RAYEN_WL_ABL & 1)) request(next);
@@ -512,7 +553,8 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
         fetch(ts_first);
         first_walk = false;
       }
-      for (int it = 0; it < n_items; ++it) {
+      const int n_walk = n_items - ((RAYEN_WL_ABL & 64) ? 4 : 0);
+      for (int it = 0; it < n_walk; ++it) {
         RAYEN_WL_STAMP(it, 0);
         const int ts = ts_next;      // (known since the previous item: nothing in front of the burst waits for a scalar load)
         // Two passes over the item's K-steps, by product size: the 2^-11 cross products first, the leading products last
@@ -554,7 +596,9 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
         // (the item's record is requested BEHIND its MFMAs: LDS and scalar loads share a counter that hipcc can only wait
         // out in full, so a request in front of the burst would hold the MFMAs back for the scalar cache's latency)
         const MItem item = items[it];
-        ts_next = (it + 1 < n_items) ? item.qbegin : ts_first;      // (qbegin: the NEXT item's tile and shape, mfma_pair_build)
+        WlScreen sc_next;
+        if constexpr (SCREEN) sc_next = scr[it + 1];      // (a blank record behind the last item)
+        ts_next = (it + 1 < n_walk) ? item.qbegin : ts_first;      // (qbegin: the NEXT item's tile and shape, mfma_pair_build)
         if constexpr (!(RAYEN_WL_ABL & 32)) fetch(ts_next);
         RAYEN_WL_STAMP(it, 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -633,6 +677,41 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
           }
         }
         RAYEN_WL_STAMP(it, 2);
+        if constexpr (SCREEN) {
+          // ---- Screening (header): the next item opens a segment whose candidate may be provably below the running maximum
+          // of every live lane -- then its items are not walked.  The segments behind it are decided here too, until one stays.
+          if (sc_next.cnst > 0.f) {
+            WlScreen s = sc_next;
+            int nx = it + 1, ts_to = ts_next;
+            const float kmax = fmaxf(kap[0], xhalf(kap[0]));
+            for (;;) {
+              const float tb = s.cnst * nv2;
+              const float a0 = aux_lds[0][s.aux][col];
+              float ub;
+              if (!(s.span >> 16)) {
+                ub = (a0 + __builtin_amdgcn_sqrtf(fmaxf(tb, 0.f))) * s.seg_inv;
+              } else {
+                ub = pair_soc_candidate(a0, aux_lds[0][s.aux + 1][col], tb, w_inv * s.seg_inv, v_inv[0], s.f0, s.f1, v_scl[0], w_scale);
+              }
+              // (a NaN or an infinite row decides nothing: every comparison with it is false)
+              const bool below = (ub < kmax) && (nv2 < __builtin_inff());
+              if (__ballot(live[0] && !below) != 0) break;
+              nx += s.span & 0xFFFF;
+              ts_to = s.ts_after;
+              skipped += (lane == s.seg) ? 1u : 0u;
+              if (ts_to < 0) break;
+              s = scr[nx];
+              if (!(s.cnst > 0.f)) break;
+            }
+            if (nx != it + 1) {
+              // the A operands already fetched belong to a skipped item: overwritten by those of the item that does run (none
+              // left: the first item's, for the next group)
+              ts_next = ts_to < 0 ? ts_first : ts_to;
+              fetch(ts_next);
+              it = nx - 1;
+            }
+          }
+        }
       }
     }
     RAYEN_WL_STAMP(38, 1);
@@ -700,6 +779,9 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     grp = next;
   }  // persistent loop over sample groups
   if (nan_flag && bad) atomicOr(nan_flag, 1);
+  if constexpr (SCREEN) {
+    if (scr_count != nullptr && skipped != 0) atomicAdd(scr_count + lane, skipped);      // one atomic instruction per wave
+  }
 #ifdef RAYEN_WL_CLOCK
   if (probe) {
     wl_clock_buf[(blockIdx.x >> 4) * 4 + 2] = __builtin_amdgcn_s_memtime();
@@ -741,9 +823,61 @@ bool mfma_pair_wl_serves(const RayenPack* p, const PairImage* img, const float* 
   return n_groups >= min_groups_env;
 }
 
+// (pack creation, this thread: the gate's probe launch screens whatever the switch says and counts into its own buffer)
+static thread_local unsigned* wl_gate_counters = nullptr;
+
+// Which segments are worth a decision.  A decision costs vector instructions in a kernel whose vector time adds to its matrix
+// time: a set whose quadratics take turns at the maximum never skips them and ran 6-7 % SLOWER with every segment decided
+// (profiles/bench/r07_wl_screen.txt).  So, once per pack: 4 096 directions uniform in [-1, 1]^n (fixed seed; kappa and the bound
+// are homogeneous in v, only the direction matters) go through the screening instance with the counters armed, and a segment
+// that was skipped for less than a quarter of the 32-sample groups -- about where the saved MFMAs pay for the decision -- loses
+// its constant (the walk then treats its items like any other).  A pack left without a segment to screen runs the instances of
+// round 6.  Anything that goes wrong here turns screening off for the pack; the results never depend on it.
+static void wl_screen_gate(const RayenPack* p, PairImage* img) {
+  constexpr int kProbe = 4096;
+  constexpr double kMinShare = 0.25;
+  const int n = p->n;
+  auto drop = [&] {
+    (void)hipFree(img->wl_screen);
+    img->wl_screen = nullptr;
+    img->host_screen.clear();
+  };
+  std::vector<float> dirs((size_t)kProbe * n);
+  uint64_t state = 0x9E3779B97F4A7C15ull;
+  for (float& x : dirs) {
+    state = state * 6364136223846793005ull + 1442695040888963407ull;
+    x = (float)((double)(state >> 11) / (double)(1ull << 53) * 2.0 - 1.0);
+  }
+  float *dv = nullptr, *dy = nullptr;
+  unsigned* dc = nullptr;
+  unsigned counts[64] = {0};
+  bool ok = hipMalloc(&dv, dirs.size() * sizeof(float)) == hipSuccess && hipMalloc(&dy, dirs.size() * sizeof(float)) == hipSuccess &&
+            hipMalloc(&dc, sizeof(counts)) == hipSuccess &&
+            hipMemcpy(dv, dirs.data(), dirs.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemset(dc, 0, sizeof(counts)) == hipSuccess;
+  if (ok) {
+    wl_gate_counters = dc;
+    ok = mfma_pair_wl_forward(p, img, dv, kProbe, n, dy, n, nullptr, nullptr, nullptr, nullptr) == RAYEN_OK;
+    wl_gate_counters = nullptr;
+    ok = ok && hipStreamSynchronize(nullptr) == hipSuccess && hipMemcpy(counts, dc, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  if (dv) (void)hipFree(dv);
+  if (dy) (void)hipFree(dy);
+  if (dc) (void)hipFree(dc);
+  if (!ok) { drop(); return; }
+  bool any = false, changed = false;
+  for (WlScreen& s : img->host_screen) {
+    if (!(s.cnst > 0.f)) continue;
+    if ((double)counts[s.seg] < kMinShare * (kProbe / 32)) { s.cnst = 0.f; changed = true; }
+    else any = true;
+  }
+  if (!any) { drop(); return; }
+  if (changed && hipMemcpy(img->wl_screen, img->host_screen.data(), img->host_screen.size() * sizeof(WlScreen), hipMemcpyHostToDevice) != hipSuccess)
+    drop();
+}
+
 // called by rayen_pack_create (the only place that may touch function attributes)
 int mfma_pair_wl_prepare(const RayenPack* p, PairImage* img) {
-  (void)p;
   if (img == nullptr || img->nkk < 1 || img->nkk > 2 || img->n_tiles <= 0 || !img->identity) return RAYEN_OK;
   const int lds = pair_wl_lds_bytes(img);
   if (lds > 160 * 1024) return RAYEN_OK;
@@ -758,8 +892,15 @@ int mfma_pair_wl_prepare(const RayenPack* p, PairImage* img) {
   };
   want(mfma_pair_wl_kernel<1, false, kWlNT, kWlWaves>); want(mfma_pair_wl_kernel<1, true, kWlNT, kWlWaves>);
   want(mfma_pair_wl_kernel<2, false, kWlNT, kWlWaves>); want(mfma_pair_wl_kernel<2, true, kWlNT, kWlWaves>);
+  if constexpr (kWlNT == 1) {      // the screening instances (same LDS)
+    want(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true>); want(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true>);
+    want(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true>); want(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true>);
+  }
   if (!ok) return RAYEN_E_LAUNCH;
   img->wl_ready = true;
+  // (RAYEN_PAIR_SCREEN_GATE=0 at pack creation: every qualifying segment stays decided -- tests and A/B runs)
+  const char* gate_env = getenv("RAYEN_PAIR_SCREEN_GATE");
+  if (kWlNT == 1 && img->wl_screen != nullptr && !(gate_env != nullptr && gate_env[0] == '0')) wl_screen_gate(p, img);
   // the mapped instances, for the widest mapper this pack can be given (in_dim = the padded width): attributes are set HERE, never
   // on a launch path; a pack whose image leaves no room for it keeps its mapped calls on rayen_mfma_pair.hip
   const int lds_m = pair_wl_lds_bytes_mapped(img, img->nkk);
@@ -816,7 +957,8 @@ int mfma_pair_wl_forward_mapped(const RayenPack* p, const PairImage* img, const 
     auto go = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(grid), dim3(kWlWaves * 64), lds, stream, static_cast<const f16x8*>(img->Wh), img->items,
                          img->n_items, img->packs, img->y0, img->n_tiles, p->n, xc, Bc, ldx, yc, ldy, kc, ac, nan_flag,
-                         img->w_scale, img->w_inv, static_cast<const f16x8*>(image), in_dim, voc, ldvo);
+                         img->w_scale, img->w_inv, static_cast<const f16x8*>(image), in_dim, voc, ldvo,
+                         static_cast<const WlScreen*>(nullptr), static_cast<unsigned*>(nullptr));
     };
     if (img->nkk == 1) {
       if (active != nullptr) go(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 1>);
@@ -843,6 +985,10 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
   // batch whose rows span more than that goes out as several launches over whole groups (same groups, same bits).
   const int64_t ld_max = std::max<int64_t>(std::max(ldv, ldy), 1);
   const int64_t rows_max = (((int64_t)0xFFFFFFFFll / (ld_max * 4)) - 64) / (kWlNT * 32) * (kWlNT * 32);
+  // screening (header): only where the image has a segment to screen; off by rayen_pair_screen(0) -- the instances of round 6
+  const bool screen = kWlNT == 1 && img->wl_screen != nullptr &&
+                      (wl_gate_counters != nullptr || pair_screen_cell().load(std::memory_order_relaxed) != 0);
+  unsigned* const counters = wl_gate_counters != nullptr ? wl_gate_counters : pair_screen_counters_cell().load(std::memory_order_relaxed);
   for (int64_t r0 = 0; r0 < B; r0 += rows_max) {
     const int64_t Bc = std::min(B - r0, rows_max);
     const int64_t n_groups = (Bc + kWlNT * 32 - 1) / (kWlNT * 32);
@@ -856,8 +1002,21 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
     auto go = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(grid), dim3(kWlWaves * 64), lds, stream, static_cast<const f16x8*>(img->Wh), img->items,
                          img->n_items, img->packs, img->y0, img->n_tiles, p->n, vc, Bc, ldv, yc, ldy, kc, ac, nan_flag,
-                         img->w_scale, img->w_inv, static_cast<const f16x8*>(nullptr), 0, static_cast<float*>(nullptr), (int64_t)0);
+                         img->w_scale, img->w_inv, static_cast<const f16x8*>(nullptr), 0, static_cast<float*>(nullptr), (int64_t)0,
+                         screen ? img->wl_screen : nullptr, screen ? counters : nullptr);
     };
+    if constexpr (kWlNT == 1) {
+      if (screen) {
+        if (img->nkk == 1) {
+          if (active != nullptr) go(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true>);
+          else go(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true>);
+        } else {
+          if (active != nullptr) go(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true>);
+          else go(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true>);
+        }
+        continue;
+      }
+    }
     if (img->nkk == 1) {
       if (active != nullptr) go(mfma_pair_wl_kernel<1, true, kWlNT, kWlWaves>);
       else go(mfma_pair_wl_kernel<1, false, kWlNT, kWlWaves>);

@@ -9,6 +9,20 @@
 
 namespace rayen {
 
+// Side table of the W-in-LDS schedule (rayen_mfma_pair_wl.hip, round 7), one record per item and a blank one behind the last:
+// where an item is the FIRST of a quadratic / cone segment that owns its tiles, what the walk needs to decide in front of it
+// whether the whole segment can be skipped for a 32-sample group -- see "Screening" in rayen_mfma_pair_wl.hip.  MItem is not
+// touched: three inline-asm kernels read it.
+struct WlScreen {
+  float cnst;        // 0: nothing to decide here | an upper bound of lambda_max(R'R) of the segment's rows AS LAID OUT, in the
+                     // walk's scaled domain ((gW f_s)^2 folded in), rounded up by 2^-10: sum of squares <= cnst ||sv v||^2
+  int32_t span;      // items the segment spans | 1 << 16: the closer is the cone's (else the quadratic's)
+  int32_t aux;       // the closer's fields, as in the segment's MItem
+  int32_t seg;       // caller's segment index: the counter's slot (below 64)
+  float f0, f1, seg_inv;
+  int32_t ts_after;  // tile | shape of the item behind the segment (what the walk fetches when it skips), -1: the list ends
+};
+
 // two f16 pieces of every entry of gW W (gW a power of two), in the fragment order of v_mfma_f32_32x32x16_f16
 struct PairImage {
   void* Wh = nullptr;      // [n_tiles][NS][2][64] x 8 f16
@@ -28,7 +42,18 @@ struct PairImage {
   bool wl_mapped_ready = false;   // ... and their mapped instances (room for the widest mapper next to the image)
   int64_t bytes = 0;
   std::vector<MItem> host_items;   // the item list as uploaded (rayen_mfma_pair_ws8.hip deals it out to eight waves)
+  WlScreen* wl_screen = nullptr;   // [n_items + 1] on the device; null: no segment of this image can be screened
+  std::vector<WlScreen> host_screen;
 };
+
+// the side table of an item list whose tiles are b.raw (boosts applied), for the image scale gW = w_scale: empty when no
+// segment qualifies (the constant is spectral_bound_rows of rayen_tiles.h: tests/test_pair_screen_bound.py)
+std::vector<WlScreen> pair_screen_table(const TileLayout& b, double w_scale);
+
+// screening of the W-in-LDS schedule: 1 on (default), 0 off (RAYEN_PAIR_SCREEN at start-up, rayen_pair_screen afterwards)
+std::atomic<int>& pair_screen_cell();
+// the armed counter buffer (64 x uint32 on the device, slot = segment index) or null
+std::atomic<unsigned*>& pair_screen_counters_cell();
 
 // eligibility is mfma_split_eligible's
 int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes);

@@ -19,7 +19,77 @@ void mfma_pair_free(PairImage* img) {
   if (img->items) (void)hipFree(img->items);
   if (img->packs) (void)hipFree(img->packs);
   if (img->y0) (void)hipFree(img->y0);
+  if (img->wl_screen) (void)hipFree(img->wl_screen);
   delete img;
+}
+
+// Screening constants (rayen_mfma_pair_wl.hip, "Screening").  A segment qualifies when its items are contiguous from MF_FIRST
+// to MF_LAST, own their tiles (MI_QFAC / MI_SOC; a cone only with a' < 0: its closer is monotone in the sum of squares then),
+// its index fits the counter and its rows are finite.  The rows are the tile's as the MFMAs see them: a half of a shared tile
+// contributes its own 32 columns only.
+std::vector<WlScreen> pair_screen_table(const TileLayout& b, const double w_scale) {
+  const int n_items = (int)b.items.size(), np = b.n_pad;
+  std::vector<WlScreen> tab((size_t)n_items + 1);
+  std::memset(tab.data(), 0, tab.size() * sizeof(WlScreen));
+  for (WlScreen& s : tab) s.ts_after = -1;
+  bool any = false;
+  for (int i = 0; i < n_items; ++i) {
+    const MItem& first = b.items[i];
+    if ((first.type != MI_QFAC && first.type != MI_SOC) || !(first.flags & MF_FIRST)) continue;
+    int j = i;
+    while (!(b.items[j].flags & MF_LAST) && j + 1 < n_items && b.items[j + 1].type == first.type && b.items[j + 1].seg == first.seg &&
+           !(b.items[j + 1].flags & MF_FIRST))
+      ++j;
+    if (!(b.items[j].flags & MF_LAST)) continue;
+    if (first.seg < 0 || first.seg >= 64 || first.aux < 0 || !(first.seg_inv > 0.f)) continue;
+    if (first.type == MI_SOC && !(first.f1 < 0.f && std::isfinite(first.f0) && std::isfinite(first.f1))) continue;
+    std::vector<std::vector<double>> own;
+    bool finite = true;
+    for (int it = i; it <= j; ++it) {
+      const MItem& m = b.items[it];
+      const int c0 = m.shape() == MS_HALF_B ? 32 : 0, c1 = m.shape() == MS_HALF_A ? 32 : np;
+      for (int r = 0; r < 32; ++r) {
+        std::vector<double> row(np, 0.0);
+        for (int c = c0; c < c1; ++c) {
+          row[c] = b.raw[((size_t)m.tile() * 32 + r) * np + c];
+          finite = finite && std::isfinite(row[c]);
+        }
+        own.push_back(std::move(row));
+      }
+    }
+    if (!finite) continue;
+    std::vector<const double*> rows;
+    for (const auto& r : own) rows.push_back(r.data());
+    const double lam = spectral_bound_rows(rows, np) * w_scale * w_scale * (1.0 + std::ldexp(1.0, -10));
+    float c = (float)lam;
+    if ((double)c < lam) c = std::nextafter(c, INFINITY);
+    if (!(c > 0.f) || !std::isfinite(c)) continue;
+    WlScreen& s = tab[i];
+    s.cnst = c;
+    s.span = (j - i + 1) | (first.type == MI_SOC ? 1 << 16 : 0);
+    s.aux = first.aux;
+    s.seg = first.seg;
+    s.f0 = first.f0;
+    s.f1 = first.f1;
+    s.seg_inv = first.seg_inv;
+    s.ts_after = j + 1 < n_items ? b.items[j + 1].tile_shape : -1;
+    any = true;
+    i = j;
+  }
+  if (!any) tab.clear();
+  return tab;
+}
+
+std::atomic<int>& pair_screen_cell() {
+  static std::atomic<int> mode([] {
+    const char* e = std::getenv("RAYEN_PAIR_SCREEN");
+    return (e != nullptr && e[0] == '0') ? 0 : 1;
+  }());
+  return mode;
+}
+std::atomic<unsigned*>& pair_screen_counters_cell() {
+  static std::atomic<unsigned*> buf(nullptr);
+  return buf;
 }
 
 static int pair_build(const RayenPack* p, PairImage** out, int64_t* bytes, bool tri);
@@ -153,6 +223,11 @@ static int pair_build(const RayenPack* p, PairImage** out, int64_t* bytes, const
           wh[base + 64 * 8] = h2;
         }
   if (!upload_walk_image(p, b, wh, &img->Wh, &img->y0, &img->items, &img->packs, &img->bytes)) {
+    mfma_pair_free(img);
+    return RAYEN_E_ALLOC;
+  }
+  img->host_screen = pair_screen_table(b, (double)img->w_scale);
+  if (!img->host_screen.empty() && !upload_to_device(img->host_screen, &img->wl_screen, &img->bytes)) {
     mfma_pair_free(img);
     return RAYEN_E_ALLOC;
   }

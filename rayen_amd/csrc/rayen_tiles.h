@@ -233,6 +233,55 @@ inline std::vector<std::vector<double>> upper_triangular_factor(const std::vecto
   return R;
 }
 
+// Upper bound of lambda_max(R'R) for the rows R (n columns each): ||R v||^2 <= bound * ||v||^2 for every v.  The value is the
+// largest eigenvalue by the fp64 Jacobi above (the rows it returns are sqrt(lambda_j) q_j': their squared norms are the
+// eigenvalues), raised by 2^-20; it is CERTIFIED, not trusted: c I - R'R must pass a Cholesky factorisation with every pivot
+// above 2^-30 c (then c > lambda_max whatever the Jacobi did; fp64 rounding of the factorisation is 1e-14 c).  A value that
+// is not certified is replaced by min(trace, largest absolute row sum) of R'R, which bound lambda_max of a positive
+// semi-definite form by themselves.  0 for rows that are all zero; rows must be finite.
+inline double spectral_bound_rows(const std::vector<const double*>& rows, int n) {
+  std::vector<double> G((size_t)n * n, 0.0);
+  for (const double* r : rows) {
+    if (r == nullptr) continue;
+    for (int i = 0; i < n; ++i) {
+      if (r[i] == 0.0) continue;
+      for (int j = 0; j < n; ++j) G[(size_t)i * n + j] += r[i] * r[j];
+    }
+  }
+  double trace = 0.0, row_sum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    trace += G[(size_t)i * n + i];
+    double s = 0.0;
+    for (int j = 0; j < n; ++j) s += std::fabs(G[(size_t)i * n + j]);
+    row_sum = s > row_sum ? s : row_sum;
+  }
+  const double safe = (trace < row_sum ? trace : row_sum) * (1.0 + 1e-12);
+  if (!(safe > 0.0)) return 0.0;
+  double lam = 0.0;
+  for (const auto& u : psd_factor_rows(G.data(), n)) {
+    double s = 0.0;
+    for (const double x : u) s += x * x;
+    lam = s > lam ? s : lam;
+  }
+  const double c = lam * (1.0 + std::ldexp(1.0, -20));
+  if (!(c > 0.0) || !(c < safe)) return safe;
+  std::vector<double> L((size_t)n * n, 0.0);      // Cholesky of c I - G, lower triangle
+  const double floor_pivot = std::ldexp(c, -30);
+  for (int j = 0; j < n; ++j) {
+    double d = c - G[(size_t)j * n + j];
+    for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
+    if (!(d > floor_pivot)) return safe;
+    const double root = std::sqrt(d);
+    L[(size_t)j * n + j] = root;
+    for (int i = j + 1; i < n; ++i) {
+      double x = -G[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) x -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
+      L[(size_t)i * n + j] = x / root;
+    }
+  }
+  return c;
+}
+
 // allow_sym = false: every quadratic / cone is laid out through a factor (rows u with ||U v||^2 = v'Gv), so
 // that no epilogue needs the direction itself (the split-operand kernel keeps v only as bf16 pieces).
 // tri (f16-pair image, with allow_sym = false, n_pad = 64): factors of more than 32 rows are made upper triangular
