@@ -176,8 +176,11 @@ int rayen_pair_schedule(int mode);
  * segments; in front of a quadratic / cone that owns its tiles the walk bounds the segment's candidate for the 32 samples
  * of a group (spectral constant of the rows as laid out x ||v||^2, through the segment's own closer) and skips its tiles
  * when the bound is below the running maximum of every live sample -- same y, kappa and record bit for bit
- * (rayen_amd/csrc/rayen_mfma_pair_wl.hip, "Screening").  1 (default): on for calls without the fused mapper | 0: off, the
- * instances of round 6.  Initial value from RAYEN_PAIR_SCREEN.  Any other mode only queries.  Returns the previous setting. */
+ * (rayen_amd/csrc/rayen_mfma_pair_wl.hip, "Screening").  Round 8 adds a second, tight test behind the spectral one: the
+ * segment's leading f16 products alone (a third of its MFMAs) plus a proved margin for the dropped ones ("Probe"); a probe
+ * skip counts into the same per-segment slot.  1 (default): both tests, for calls without the fused mapper | 2: the spectral
+ * test alone (round 7's behaviour, for A/B) | 0: off, the instances of round 6.  Initial value from RAYEN_PAIR_SCREEN.  Any
+ * other mode only queries.  Returns the previous setting. */
 int rayen_pair_screen(int mode);
 /* Arm (device_counts: 64 x uint32 of device memory, zeroed by the caller) or disarm (NULL) the screening counters: while
  * armed, every screening launch ADDS to device_counts[s] the number of 32-sample groups for which segment s was skipped

@@ -120,6 +120,7 @@ def load():
     lib.rayen_last_forward_kernel.argtypes = []
     lib.rayen_pair_schedule.restype = ctypes.c_int
     lib.rayen_pair_schedule.argtypes = [ctypes.c_int]
+    # (mode: 1 spectral test and leading-product probe (default) | 2 spectral test only | 0 off | anything else queries)
     lib.rayen_pair_screen.restype = ctypes.c_int
     lib.rayen_pair_screen.argtypes = [ctypes.c_int]
     lib.rayen_pair_screen_counters.restype = ctypes.c_int

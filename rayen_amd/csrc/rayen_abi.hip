@@ -461,7 +461,7 @@ int rayen_pair_schedule(int mode) {
 }
 
 int rayen_pair_screen(int mode) {
-  if (mode == 0 || mode == 1) return pair_screen_cell().exchange(mode, std::memory_order_relaxed);
+  if (mode == 0 || mode == 1 || mode == 2) return pair_screen_cell().exchange(mode, std::memory_order_relaxed);
   return pair_screen_cell().load(std::memory_order_relaxed);
 }
 

@@ -46,6 +46,39 @@
 // never beats the running maximum.  So ub >= the candidate, and a skipped candidate would have lost every comparison:
 // same bits (tests/test_gpu_pair_wl_screen.py, and every bit-for-bit test of the four schedules).
 //
+// Probe (round 8; same instances, mode 1 of rayen_pair_screen): the spectral bound is lambda_max ||v||^2, and a quadratic's
+// true sum of squares sits near a quarter of it (config 3), so that test fires only when the running maximum is twice the
+// candidate -- for the cones, never for the quadratics.  A tight test is cheap: the walk rebuilds every fp32 product from three
+// f16 products a2 b1, a1 b2, a1 b1, and the LEADING one alone gives the accumulator to 2^-10.  Where the spectral test leaves a
+// segment standing and its record carries a probe constant (WlScreen::cabs), the wave reads only the leading pieces a1 of the
+// segment's items from LDS, runs  p = sum_sp a1 vb[0][0][sp]  per item from zero (a third of the MFMAs; acc and part are dead
+// between two segments), sums the squares across the items exactly as the epilogue does, and forms
+//   ub_total = (sqrt(total_probe) + sqrt(cabs nv2))^2 (1 + 2^-12),   ub = closer(aux rows, ub_total)
+// with the segment's OWN closer; the segment is skipped iff ub < max(kap, other half's kap) on every live lane, nv2 < inf, and
+// the row is one the margin is proved for (below).  Skipped: the segments behind it are decided at the same point.  Not skipped:
+// the segment is walked as always -- both pieces fetched, the products in their order, nothing of the probe reused.
+//   Why ub_total dominates the sum of squares the walk would have computed.  Write a = the scaled fp32 entry of the image,
+// a1 = f16(a), a2 = f16(a - a1), x = sv v, b1 = f16(x), b2 = f16(x - b1) (round to nearest: the image and pair_split_*).  In exact
+// arithmetic the walk's accumulator is F_i = sum_k (a2 b1 + a1 b2 + a1 b1), the probe's P_i = sum_k a1 b1.  |a2| <= 2^-11 (1 +
+// 2^-10) |a| + 2^-24 and |a1| <= (1 + 2^-11) |a| + 2^-25 (the absolute terms: pieces below 2^-14 are f16 subnormals), the same
+// for b2, b1 against x, so  |F_i - P_i| <= 2^-10 (1 + 2^-9) sum_k |a_ik| |x_k| + 2^-23 (||a_i||_1 + ||x||_1) + 2^-42.  For a row
+// whose largest scaled entry reached 2^13 -- pow2_scale puts it into [2^13, 2^14) unless max |v| < 2^-113, where the scale is
+// clamped; the kernel tests nv2 >= 2^26 and takes the zero row, whose products all vanish, as well -- ||a_i||_1 <= 8 ||a_i||_2
+// <= 2^-10 ||a_i||_2 ||x||, so the 2-norm over the segment's m rows is
+//   ||F - P|| <= (2^-10 (1 + 2^-9 + 2^-20) || |R| ||_2 + 2^-20 sqrt(m)) ||x||,
+// |R| the rows as laid out, entrywise absolute, in the scaled domain.  The fp32 accumulation of the 192 products of F and the
+// 64 of P adds at most 2^-16 sum_k |a| |x| per row.  cabs = (2^-10 (1 + 2^-4) sqrt(lambda_max(|R|'|R|)) gW f_s + 2^-19 sqrt(m))^2,
+// rounded up (rayen_tiles.h::pair_probe_constant: spectral_bound_rows of the absolute rows, Cholesky certificate included;
+// tests/test_pair_probe_bound.py: no direction uses more than 0.13 of it), covers both with room.  The two sums of squares are
+// fp32 sums of at most 64 non-negative terms per lane and a pair of adds (relative error 2^-18 each, either direction), nv2
+// carries 2^-19, the two v_sqrt_f32 one ulp each, the product, the sum and the square a rounding each: below 2^-15 of ub_total
+// together, paid by the factor 1 + 2^-12.  So ub_total >= the walk's fp32 total, the closers are monotone in it (above), and
+// a skipped candidate would have lost every comparison: same bits (tests/test_gpu_pair_wl_probe.py).
+//   Order (round 8): the probe pays only against a high running maximum, so this schedule walks its own copy of the item list
+// in which the quadratics / cones of a run of adjacent segments come in the order of how often each sets kappa on the
+// pack-creation directions (wl_screen_gate, pair_wl_reorder).  A candidate's bits do not depend on its place and kappa is a
+// maximum; the other schedules keep the shared list, so their bit-for-bit tests against this one cover the permutation.
+//
 // Served: NA_E = I, n = k in (32 (NKK - 1), 32 NKK] and a multiple of 4, rows 16-byte aligned, the image + the aux patches within 160 KiB of LDS, at most
 // sixteen aux rows at NKK = 2 (eight behind a mapper).  Everything else stays on the other schedules.
 #include "rayen_split_image.h"
@@ -159,7 +192,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     float* __restrict__ kappa_out, int32_t* __restrict__ active_out,
     int32_t* __restrict__ nan_flag, const float w_scale, const float w_inv,
     const f16x8* __restrict__ mimg, int n_in, float* __restrict__ v_out, int64_t ldvo,
-    const WlScreen* __restrict__ scr, unsigned* __restrict__ scr_count) {
+    const WlScreen* __restrict__ scr, unsigned* __restrict__ scr_count, const int probe_on) {
   static_assert(!SCREEN || (NT == 1 && NKX == 0), "screening: one sample tile per wave, no mapper in front");
   constexpr int NS = NKK * 2, NCH = NS * 2, NQ = NKK * 4, AUXR = WlGeom<NKK, (NKX > 0)>::AUXR;
   constexpr int NSX = NKX * 2, NQX = NKX * 4, MCH = NKK * NSX * 2;   // the mapper's K-steps, row pieces, 1-KiB chunks
@@ -680,36 +713,95 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
         if constexpr (SCREEN) {
           // ---- Screening (header): the next item opens a segment whose candidate may be provably below the running maximum
           // of every live lane -- then its items are not walked.  The segments behind it are decided here too, until one stays.
-          if (sc_next.cnst > 0.f) {
+          if (sc_next.cnst > 0.f || sc_next.cabs > 0.f) {
             WlScreen s = sc_next;
             int nx = it + 1, ts_to = ts_next;
-            const float kmax = fmaxf(kap[0], xhalf(kap[0]));
+            int ts_held = ts_next;      // the item whose operands abuf holds in full (-2: a probe has overwritten leading pieces)
+            auto kmax_now = [&] { return fmaxf(kap[0], xhalf(kap[0])); };
+            // (a NaN or an infinite row decides nothing: every comparison with it is false)
+            const bool nv_ok = nv2 < __builtin_inff();
+            // (the probe's margin is proved for a row whose largest scaled entry reached 2^13 -- every row but one below 2^-113,
+            // where the scale is clamped -- and for the zero row, whose products are all zero)
+            const bool probe_row = (nv2 >= 67108864.f) || (nv2 == 0.f);
             for (;;) {
-              const float tb = s.cnst * nv2;
-              const float a0 = aux_lds[0][s.aux][col];
-              float ub;
-              if (!(s.span >> 16)) {
-                ub = (a0 + __builtin_amdgcn_sqrtf(fmaxf(tb, 0.f))) * s.seg_inv;
-              } else {
-                ub = pair_soc_candidate(a0, aux_lds[0][s.aux + 1][col], tb, w_inv * s.seg_inv, v_inv[0], s.f0, s.f1, v_scl[0], w_scale);
+              bool skip = false;
+              if (s.cnst > 0.f) {
+                const float tb = s.cnst * nv2;
+                const float a0 = aux_lds[0][s.aux][col];
+                float ub;
+                if (!(s.span >> 16)) {
+                  ub = (a0 + __builtin_amdgcn_sqrtf(fmaxf(tb, 0.f))) * s.seg_inv;
+                } else {
+                  ub = pair_soc_candidate(a0, aux_lds[0][s.aux + 1][col], tb, w_inv * s.seg_inv, v_inv[0], s.f0, s.f1, v_scl[0], w_scale);
+                }
+                const bool below = (ub < kmax_now()) && nv_ok;
+                skip = __ballot(live[0] && !below) == 0;
               }
-              // (a NaN or an infinite row decides nothing: every comparison with it is false)
-              const bool below = (ub < kmax) && (nv2 < __builtin_inff());
-              if (__ballot(live[0] && !below) != 0) break;
+              if (!skip && probe_on != 0 && s.cabs > 0.f) {
+                // ---- Probe (header): the segment's sum of squares from the LEADING products a1 b1 alone, a third of the MFMAs,
+                // into acc / part (dead between two segments); only the leading pieces of its items are read from LDS
+                const int span = s.span & 0xFFFF;
+                int ts_j = ts_to;
+                for (int j = 0; j < span; ++j) {
+                  const char* tb = wimg + (size_t)(ts_j & 0xFFFFFF) * (NCH * 1024) + lane * 16;
+                  const int shape = NS == 4 ? __builtin_amdgcn_readfirstlane((ts_j >> 24) & 3) : MS_FULL;
+                  auto lead = [&](auto S0, auto S1) {
+                    constexpr int s0 = decltype(S0)::value, s1 = decltype(S1)::value;
+                    if (ts_j != ts_held) {
+#pragma unroll
+                      for (int sp = s0; sp < s1; ++sp) abuf[2 * sp] = *reinterpret_cast<const u32x4*>(tb + (2 * sp) * 1024);
+                      ts_held = -2;
+                    }
+#pragma unroll
+                    for (int sp = s0; sp < s1; ++sp)
+                      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, abuf[2 * sp]), vb[0][0][sp],
+                                                                      sp == s0 ? zero : acc[0], 0, 0, 0);
+                  };
+                  if constexpr (NS == 4) {
+                    if (shape == MS_FULL) lead(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
+                    else if (shape == MS_HALF_A) lead(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+                    else lead(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
+                  } else {
+                    lead(std::integral_constant<int, 0>{}, std::integral_constant<int, NS>{});
+                  }
+                  if (j + 1 < span) ts_j = items[nx + j].qbegin;
+                  float s0 = j == 0 ? 0.f : part[0], s1 = 0.f;
+#pragma unroll
+                  for (int g = 0; g < 16; g += 2) {
+                    s0 = fmaf(acc[0][g], acc[0][g], s0);
+                    s1 = fmaf(acc[0][g + 1], acc[0][g + 1], s1);
+                  }
+                  part[0] = s0 + s1;
+                }
+                const float total = part[0] + xhalf(part[0]);
+                const float r = __builtin_amdgcn_sqrtf(fmaxf(total, 0.f)) + __builtin_amdgcn_sqrtf(s.cabs * nv2);
+                const float tb = (r * r) * 1.000244140625f;      // (1 + 2^-12: the fp32 roundings of both sums and of this line)
+                const float a0 = aux_lds[0][s.aux][col];
+                float ub;
+                if (!(s.span >> 16)) {
+                  ub = (a0 + __builtin_amdgcn_sqrtf(fmaxf(tb, 0.f))) * s.seg_inv;
+                } else {
+                  ub = pair_soc_candidate(a0, aux_lds[0][s.aux + 1][col], tb, w_inv * s.seg_inv, v_inv[0], s.f0, s.f1, v_scl[0], w_scale);
+                }
+                const bool below = (ub < kmax_now()) && nv_ok && probe_row;
+                skip = __ballot(live[0] && !below) == 0;
+              }
+              if (!skip) break;
               nx += s.span & 0xFFFF;
               ts_to = s.ts_after;
               skipped += (lane == s.seg) ? 1u : 0u;
               if (ts_to < 0) break;
               s = scr[nx];
-              if (!(s.cnst > 0.f)) break;
+              if (!(s.cnst > 0.f) && !(s.cabs > 0.f)) break;
             }
             if (nx != it + 1) {
-              // the A operands already fetched belong to a skipped item: overwritten by those of the item that does run (none
+              // the A operands already fetched belong to a skipped item: those of the item that does run are fetched below (none
               // left: the first item's, for the next group)
               ts_next = ts_to < 0 ? ts_first : ts_to;
-              fetch(ts_next);
               it = nx - 1;
             }
+            // (a probe that failed on a segment of several items, or ran behind a skipped segment, has overwritten leading pieces)
+            if (ts_held != ts_next) fetch(ts_next);
           }
         }
       }
@@ -823,24 +915,36 @@ bool mfma_pair_wl_serves(const RayenPack* p, const PairImage* img, const float* 
   return n_groups >= min_groups_env;
 }
 
-// (pack creation, this thread: the gate's probe launch screens whatever the switch says and counts into its own buffer)
+// (pack creation, this thread: the gate's launches choose their own mode, whatever the switch says, and count into their own buffer)
 static thread_local unsigned* wl_gate_counters = nullptr;
+static thread_local int wl_gate_mode = 1;      // 0: the instances of round 6 (the ordering launch) | 2: spectral test only | 1: both
 
-// Which segments are worth a decision.  A decision costs vector instructions in a kernel whose vector time adds to its matrix
-// time: a set whose quadratics take turns at the maximum never skips them and ran 6-7 % SLOWER with every segment decided
-// (profiles/bench/r07_wl_screen.txt).  So, once per pack: 4 096 directions uniform in [-1, 1]^n (fixed seed; kappa and the bound
-// are homogeneous in v, only the direction matters) go through the screening instance with the counters armed, and a segment
-// that was skipped for less than a quarter of the 32-sample groups -- about where the saved MFMAs pay for the decision -- loses
-// its constant (the walk then treats its items like any other).  A pack left without a segment to screen runs the instances of
-// round 6.  Anything that goes wrong here turns screening off for the pack; the results never depend on it.
-static void wl_screen_gate(const RayenPack* p, PairImage* img) {
+// Which segments are worth a decision, and in which order this schedule walks them.  A decision costs vector instructions in
+// a kernel whose vector time adds to its matrix time: a set whose quadratics take turns at the maximum never skips them and ran
+// 6-7 % SLOWER with every segment decided (profiles/bench/r07_wl_screen.txt).  So, once per pack: 4 096 directions uniform in
+// [-1, 1]^n (fixed seed; kappa and the bounds are homogeneous in v, only the direction matters) go through
+//   1. the tracking instance of round 6: how often each segment sets kappa.  The quadratics / cones of a run of adjacent segments
+//      are walked in that order, most frequent first (pair_wl_reorder: the probe pays only against a high running maximum; a
+//      candidate's bits do not depend on its place and kappa is a maximum) -- this schedule's own copy of the list;
+//   2. (unless RAYEN_PAIR_SCREEN_GATE=0) the screening instance twice with the counters armed, spectral test alone and with the
+//      probe.  A segment the spectral test skipped for less than a quarter of the 32-sample groups loses its constant; a segment
+//      whose probe, in the groups the spectral test left to it, skipped less than kMinProbeShare loses its probe.  By MFMA count
+//      a probe breaks even at 1/3 (a skip saves two thirds of the segment, a failed probe costs one third more), the failed
+//      probe's second epilogue and re-fetch move that up: 1/2 (profiles/bench/r08_wl_probe.txt).
+// A pack left without a segment to decide runs the instances of round 6 on the shared list.  Anything that goes wrong here turns
+// screening off for the pack; the results never depend on it.
+static void wl_screen_gate(const RayenPack* p, PairImage* img, const bool gate) {
   constexpr int kProbe = 4096;
   constexpr double kMinShare = 0.25;
+  constexpr double kMinProbeShare = 0.5;
   const int n = p->n;
   auto drop = [&] {
     (void)hipFree(img->wl_screen);
     img->wl_screen = nullptr;
     img->host_screen.clear();
+    if (img->wl_items) (void)hipFree(img->wl_items);
+    img->wl_items = nullptr;
+    img->wl_host_items.clear();
   };
   std::vector<float> dirs((size_t)kProbe * n);
   uint64_t state = 0x9E3779B97F4A7C15ull;
@@ -850,26 +954,63 @@ static void wl_screen_gate(const RayenPack* p, PairImage* img) {
   }
   float *dv = nullptr, *dy = nullptr;
   unsigned* dc = nullptr;
-  unsigned counts[64] = {0};
-  bool ok = hipMalloc(&dv, dirs.size() * sizeof(float)) == hipSuccess && hipMalloc(&dy, dirs.size() * sizeof(float)) == hipSuccess &&
-            hipMalloc(&dc, sizeof(counts)) == hipSuccess &&
-            hipMemcpy(dv, dirs.data(), dirs.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemset(dc, 0, sizeof(counts)) == hipSuccess;
-  if (ok) {
+  int32_t* da = nullptr;
+  unsigned counts_s[64] = {0}, counts_b[64] = {0};
+  std::vector<int32_t> act((size_t)2 * kProbe, -1);
+  auto launch = [&](const int mode, int32_t* active) {
     wl_gate_counters = dc;
-    ok = mfma_pair_wl_forward(p, img, dv, kProbe, n, dy, n, nullptr, nullptr, nullptr, nullptr) == RAYEN_OK;
+    wl_gate_mode = mode;
+    const bool fine = mfma_pair_wl_forward(p, img, dv, kProbe, n, dy, n, nullptr, active, nullptr, nullptr) == RAYEN_OK;
     wl_gate_counters = nullptr;
-    ok = ok && hipStreamSynchronize(nullptr) == hipSuccess && hipMemcpy(counts, dc, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
+    wl_gate_mode = 1;
+    return fine && hipStreamSynchronize(nullptr) == hipSuccess;
+  };
+  bool ok = hipMalloc(&dv, dirs.size() * sizeof(float)) == hipSuccess && hipMalloc(&dy, dirs.size() * sizeof(float)) == hipSuccess &&
+            hipMalloc(&dc, sizeof(counts_s)) == hipSuccess && hipMalloc(&da, act.size() * sizeof(int32_t)) == hipSuccess &&
+            hipMemcpy(dv, dirs.data(), dirs.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemset(dc, 0, sizeof(counts_s)) == hipSuccess;
+  // ---- 1. the order
+  ok = ok && launch(0, da) && hipMemcpy(act.data(), da, act.size() * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+  if (ok) {
+    std::vector<uint64_t> hits(p->segs.size(), 0);
+    for (int r = 0; r < kProbe; ++r) {
+      const int32_t sg = act[(size_t)2 * r];
+      if (sg >= 0 && (size_t)sg < hits.size()) ++hits[sg];
+    }
+    std::vector<MItem> own = img->host_items;
+    std::vector<WlScreen> tab = img->host_screen;
+    if (pair_wl_reorder(own, tab, hits)) {
+      ok = upload_to_device(own, &img->wl_items, &img->bytes) &&
+           hipMemcpy(img->wl_screen, tab.data(), tab.size() * sizeof(WlScreen), hipMemcpyHostToDevice) == hipSuccess;
+      if (ok) {
+        img->wl_host_items.swap(own);
+        img->host_screen.swap(tab);
+      }
+    }
+  }
+  // ---- 2. the gate
+  if (ok && gate) {
+    ok = launch(2, nullptr) && hipMemcpy(counts_s, dc, sizeof(counts_s), hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemset(dc, 0, sizeof(counts_s)) == hipSuccess && launch(1, nullptr) &&
+         hipMemcpy(counts_b, dc, sizeof(counts_b), hipMemcpyDeviceToHost) == hipSuccess;
   }
   if (dv) (void)hipFree(dv);
   if (dy) (void)hipFree(dy);
   if (dc) (void)hipFree(dc);
+  if (da) (void)hipFree(da);
   if (!ok) { drop(); return; }
+  if (!gate) return;
   bool any = false, changed = false;
+  const double groups = kProbe / 32;
   for (WlScreen& s : img->host_screen) {
-    if (!(s.cnst > 0.f)) continue;
-    if ((double)counts[s.seg] < kMinShare * (kProbe / 32)) { s.cnst = 0.f; changed = true; }
-    else any = true;
+    if (!(s.cnst > 0.f) && !(s.cabs > 0.f)) continue;
+    const double by_bound = counts_s[s.seg], by_both = counts_b[s.seg] > counts_s[s.seg] ? counts_b[s.seg] : counts_s[s.seg];
+    const bool keep_bound = s.cnst > 0.f && by_bound >= kMinShare * groups;
+    const double left = keep_bound ? groups - by_bound : groups, by_probe = keep_bound ? by_both - by_bound : by_both;
+    const bool keep_probe = s.cabs > 0.f && left > 0.0 && by_probe >= kMinProbeShare * left;
+    if (!keep_bound && s.cnst > 0.f) { s.cnst = 0.f; changed = true; }
+    if (!keep_probe && s.cabs > 0.f) { s.cabs = 0.f; changed = true; }
+    any = any || keep_bound || keep_probe;
   }
   if (!any) { drop(); return; }
   if (changed && hipMemcpy(img->wl_screen, img->host_screen.data(), img->host_screen.size() * sizeof(WlScreen), hipMemcpyHostToDevice) != hipSuccess)
@@ -900,7 +1041,7 @@ int mfma_pair_wl_prepare(const RayenPack* p, PairImage* img) {
   img->wl_ready = true;
   // (RAYEN_PAIR_SCREEN_GATE=0 at pack creation: every qualifying segment stays decided -- tests and A/B runs)
   const char* gate_env = getenv("RAYEN_PAIR_SCREEN_GATE");
-  if (kWlNT == 1 && img->wl_screen != nullptr && !(gate_env != nullptr && gate_env[0] == '0')) wl_screen_gate(p, img);
+  if (kWlNT == 1 && img->wl_screen != nullptr) wl_screen_gate(p, img, !(gate_env != nullptr && gate_env[0] == '0'));
   // the mapped instances, for the widest mapper this pack can be given (in_dim = the padded width): attributes are set HERE, never
   // on a launch path; a pack whose image leaves no room for it keeps its mapped calls on rayen_mfma_pair.hip
   const int lds_m = pair_wl_lds_bytes_mapped(img, img->nkk);
@@ -958,7 +1099,7 @@ int mfma_pair_wl_forward_mapped(const RayenPack* p, const PairImage* img, const 
       hipLaunchKernelGGL(kern, dim3(grid), dim3(kWlWaves * 64), lds, stream, static_cast<const f16x8*>(img->Wh), img->items,
                          img->n_items, img->packs, img->y0, img->n_tiles, p->n, xc, Bc, ldx, yc, ldy, kc, ac, nan_flag,
                          img->w_scale, img->w_inv, static_cast<const f16x8*>(image), in_dim, voc, ldvo,
-                         static_cast<const WlScreen*>(nullptr), static_cast<unsigned*>(nullptr));
+                         static_cast<const WlScreen*>(nullptr), static_cast<unsigned*>(nullptr), 0);
     };
     if (img->nkk == 1) {
       if (active != nullptr) go(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 1>);
@@ -986,9 +1127,13 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
   const int64_t ld_max = std::max<int64_t>(std::max(ldv, ldy), 1);
   const int64_t rows_max = (((int64_t)0xFFFFFFFFll / (ld_max * 4)) - 64) / (kWlNT * 32) * (kWlNT * 32);
   // screening (header): only where the image has a segment to screen; off by rayen_pair_screen(0) -- the instances of round 6
-  const bool screen = kWlNT == 1 && img->wl_screen != nullptr &&
-                      (wl_gate_counters != nullptr || pair_screen_cell().load(std::memory_order_relaxed) != 0);
+  // (mode 2: the spectral test alone, round 7's behaviour; the gate's launches choose for themselves)
+  const int mode = wl_gate_counters != nullptr ? wl_gate_mode : pair_screen_cell().load(std::memory_order_relaxed);
+  const bool screen = kWlNT == 1 && img->wl_screen != nullptr && mode != 0;
+  const int probe_on = mode == 1 ? 1 : 0;
   unsigned* const counters = wl_gate_counters != nullptr ? wl_gate_counters : pair_screen_counters_cell().load(std::memory_order_relaxed);
+  // (round 8: this schedule's own order of the list, where pack creation found one)
+  const MItem* const items = img->wl_items != nullptr ? img->wl_items : img->items;
   for (int64_t r0 = 0; r0 < B; r0 += rows_max) {
     const int64_t Bc = std::min(B - r0, rows_max);
     const int64_t n_groups = (Bc + kWlNT * 32 - 1) / (kWlNT * 32);
@@ -1000,10 +1145,10 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
     float* kc = kappa ? kappa + r0 : nullptr;
     int32_t* ac = active ? active + 2 * r0 : nullptr;
     auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kWlWaves * 64), lds, stream, static_cast<const f16x8*>(img->Wh), img->items,
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(kWlWaves * 64), lds, stream, static_cast<const f16x8*>(img->Wh), items,
                          img->n_items, img->packs, img->y0, img->n_tiles, p->n, vc, Bc, ldv, yc, ldy, kc, ac, nan_flag,
                          img->w_scale, img->w_inv, static_cast<const f16x8*>(nullptr), 0, static_cast<float*>(nullptr), (int64_t)0,
-                         screen ? img->wl_screen : nullptr, screen ? counters : nullptr);
+                         screen ? img->wl_screen : nullptr, screen ? counters : nullptr, probe_on);
     };
     if constexpr (kWlNT == 1) {
       if (screen) {

@@ -6,6 +6,7 @@
 // scaling are described at the top of rayen_mfma_pair.hip.
 #include "rayen_pair_image.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +21,7 @@ void mfma_pair_free(PairImage* img) {
   if (img->packs) (void)hipFree(img->packs);
   if (img->y0) (void)hipFree(img->y0);
   if (img->wl_screen) (void)hipFree(img->wl_screen);
+  if (img->wl_items) (void)hipFree(img->wl_items);
   delete img;
 }
 
@@ -73,6 +75,11 @@ std::vector<WlScreen> pair_screen_table(const TileLayout& b, const double w_scal
     s.f1 = first.f1;
     s.seg_inv = first.seg_inv;
     s.ts_after = j + 1 < n_items ? b.items[j + 1].tile_shape : -1;
+    // the probe constant (round 8, "Probe" in rayen_mfma_pair_wl.hip): the same rows, entrywise absolute
+    const double ca = pair_probe_constant(rows, np, w_scale);
+    float cf = (float)ca;
+    if ((double)cf < ca) cf = std::nextafter(cf, INFINITY);
+    s.cabs = (cf > 0.f && std::isfinite(cf)) ? cf : 0.f;
     any = true;
     i = j;
   }
@@ -80,10 +87,66 @@ std::vector<WlScreen> pair_screen_table(const TileLayout& b, const double w_scal
   return tab;
 }
 
+bool pair_wl_reorder(std::vector<MItem>& items, std::vector<WlScreen>& screen, const std::vector<uint64_t>& hits) {
+  const int n_items = (int)items.size();
+  if ((int)screen.size() != n_items + 1) return false;
+  struct Block { int first, count; uint64_t hits; };
+  // blocks of the list: a whole segment (FIRST .. LAST, one type, one index) or a single item of anything else
+  std::vector<Block> blocks;
+  std::vector<char> is_seg;
+  for (int i = 0; i < n_items;) {
+    const MItem& f = items[i];
+    int j = i;
+    bool seg = (f.type == MI_QFAC || f.type == MI_SOC) && (f.flags & MF_FIRST);
+    if (seg) {
+      while (!(items[j].flags & MF_LAST) && j + 1 < n_items && items[j + 1].type == f.type && items[j + 1].seg == f.seg &&
+             !(items[j + 1].flags & MF_FIRST))
+        ++j;
+      if (!(items[j].flags & MF_LAST)) return false;
+    } else if (f.type == MI_QFAC || f.type == MI_SOC) {
+      return false;
+    }
+    const uint64_t h = seg && f.seg >= 0 && (size_t)f.seg < hits.size() ? hits[f.seg] : 0;
+    blocks.push_back({i, j - i + 1, h});
+    is_seg.push_back(seg ? 1 : 0);
+    i = j + 1;
+  }
+  bool moved = false;
+  std::vector<Block> order = blocks;
+  for (size_t a = 0; a < order.size();) {
+    size_t e = a;
+    while (e < order.size() && is_seg[e]) ++e;
+    if (e > a + 1) {
+      std::stable_sort(order.begin() + a, order.begin() + e, [](const Block& x, const Block& y) { return x.hits > y.hits; });
+      for (size_t k = a; k < e; ++k) moved = moved || order[k].first != blocks[k].first;
+    }
+    a = e > a ? e : a + 1;
+  }
+  if (!moved) return false;
+  std::vector<MItem> out_items;
+  std::vector<WlScreen> out_screen;
+  for (const Block& bl : order)
+    for (int k = 0; k < bl.count; ++k) {
+      out_items.push_back(items[bl.first + k]);
+      out_screen.push_back(screen[bl.first + k]);
+    }
+  out_screen.push_back(screen[n_items]);
+  for (int i = 0; i < n_items; ++i) out_items[i].qbegin = out_items[i + 1 < n_items ? i + 1 : i].tile_shape;
+  for (int i = 0; i < n_items; ++i) {
+    WlScreen& s = out_screen[i];
+    if (!(s.cnst > 0.f) && !(s.cabs > 0.f)) continue;
+    const int behind = i + (s.span & 0xFFFF);
+    s.ts_after = behind < n_items ? out_items[behind].tile_shape : -1;
+  }
+  items.swap(out_items);
+  screen.swap(out_screen);
+  return true;
+}
+
 std::atomic<int>& pair_screen_cell() {
   static std::atomic<int> mode([] {
     const char* e = std::getenv("RAYEN_PAIR_SCREEN");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
+    return (e != nullptr && e[0] == '0') ? 0 : ((e != nullptr && e[0] == '2') ? 2 : 1);
   }());
   return mode;
 }

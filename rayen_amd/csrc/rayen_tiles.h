@@ -282,6 +282,31 @@ inline double spectral_bound_rows(const std::vector<const double*>& rows, int n)
   return c;
 }
 
+// The probe constant of the W-in-LDS walk (rayen_mfma_pair_wl.hip, "Probe"): cabs with
+//   || full accumulators || <= || leading-product accumulators || + sqrt(cabs) ||x||
+// for the rows R (already in the walk's scaled domain up to the factor `scale` = gW; largest scaled entry below 2^14) against
+// every scaled direction x = sv v whose largest entry is in [2^13, 2^14).  sqrt(cabs) = 2^-10 (1 + 2^-4) ||(|R|)||_2 scale
+// + 2^-19 sqrt(rows): the first term is the two dropped products (|a2| <= 2^-11 |a|, |b2| <= 2^-11 |x| up to 1 + 2^-10 each)
+// with room for the fp32 accumulation of both accumulators, the second the f16 subnormals (a piece below 2^-14 is off by up
+// to 2^-24 absolutely, not relatively).  ||(|R|)||_2^2 is spectral_bound_rows of the absolute rows, certificate included.
+// 0 for rows that are all zero (nothing to probe).  tests/test_pair_probe_bound.py.
+inline double pair_probe_constant(const std::vector<const double*>& rows, int n, double scale) {
+  std::vector<std::vector<double>> abs_rows;
+  std::vector<const double*> ptr;
+  for (const double* r : rows) {
+    if (r == nullptr) continue;
+    std::vector<double> a(n);
+    for (int j = 0; j < n; ++j) a[j] = std::fabs(r[j]);
+    abs_rows.push_back(std::move(a));
+  }
+  for (const auto& a : abs_rows) ptr.push_back(a.data());
+  const double lam = spectral_bound_rows(ptr, n);
+  if (!(lam > 0.0)) return 0.0;
+  const double m = std::ldexp(1.0 + std::ldexp(1.0, -4), -10) * std::sqrt(lam) * scale * (1.0 + 1e-12) +
+                   std::ldexp(std::sqrt((double)rows.size()), -19);
+  return m * m * (1.0 + 1e-12);
+}
+
 // allow_sym = false: every quadratic / cone is laid out through a factor (rows u with ||U v||^2 = v'Gv), so
 // that no epilogue needs the direction itself (the split-operand kernel keeps v only as bf16 pieces).
 // tri (f16-pair image, with allow_sym = false, n_pad = 64): factors of more than 32 rows are made upper triangular
