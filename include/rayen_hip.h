@@ -539,6 +539,7 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 
 /* ---- Wide sets (n > 128) in one launch, without the products matrix of the ABI v7 route (additive to ABI v15) */
 #include "rayen_hip_wide_fused.h"
+#include "rayen_hip_wide_fused_bwd.h"
 
 #ifdef __cplusplus
 }

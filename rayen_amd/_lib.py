@@ -58,6 +58,10 @@ EXPORTS_BAR_STREAM = ("rayen_bar_resident_served", "rayen_bar_stream_forward_f32
 # additive to ABI v15, declared in include/rayen_hip_wide_fused.h (which rayen_hip.h includes, like the four above);
 # tests/test_wide_fused_host.py holds the two against each other
 EXPORTS_WIDE_FUSED = ("rayen_wide_fused_served", "rayen_ray_project_wide_fused_f32")
+# additive to ABI v15, declared in include/rayen_hip_wide_fused_bwd.h (which rayen_hip.h includes, like the five above);
+# tests/test_wide_fused_bwd_host.py holds the two against each other
+EXPORTS_WIDE_FUSED_BWD = ("rayen_wide_fused_bwd_served", "rayen_wide_fused_bwd_workspace_bytes",
+                          "rayen_ray_project_wide_fused_bwd_f32")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 KERNEL_WIDE_FUSED = 12
 
@@ -149,6 +153,12 @@ def load():
         getattr(lib, name).argtypes = [p, p, i64, p, i64, i64, p, i32p, p, i64, p, i64, p, p]
     lib.rayen_wide_fused_served.restype = ctypes.c_int
     lib.rayen_wide_fused_served.argtypes = [p, ctypes.c_int32]
+    lib.rayen_wide_fused_bwd_served.restype = ctypes.c_int
+    lib.rayen_wide_fused_bwd_served.argtypes = [p, ctypes.c_int32]
+    lib.rayen_wide_fused_bwd_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_wide_fused_bwd_workspace_bytes.argtypes = [p, i64]
+    lib.rayen_ray_project_wide_fused_bwd_f32.restype = ctypes.c_int
+    lib.rayen_ray_project_wide_fused_bwd_f32.argtypes = [p, p, i64, i64, p, i32p, p, i64, p, i64, p, i64, p]
     lib.rayen_products_rows.restype = ctypes.c_int64
     lib.rayen_products_rows.argtypes = [p]
     lib.rayen_products_served.restype = ctypes.c_int

@@ -66,13 +66,16 @@ class ConstraintModule(torch.nn.Module):
     def _route_key(self, old_head=False):
         """Third part of a refusal's key: the old head of RAYEN_old, the kernel ``args_DC3`` asks for (``False`` for the
         default, ``'lane'``), the kernel ``bar_kernel`` asks for (``False`` for the default, ``'resident'``), the kernel
-        ``wide_kernel`` asks for under method 'RAYEN' (``False`` for the default, ``'products'``), ``False`` otherwise."""
+        ``wide_kernel`` asks for under method 'RAYEN' (``False`` for the default, ``'products'``; with a ``wide_backward``
+        other than the default, ``'<wide_kernel>+bwd_<wide_backward>'``), ``False`` otherwise."""
         if self.method == 'DC3':
             kernel = _dc3.kernel_choice(self.args_DC3)
             return False if kernel == 'lane' else kernel
         if self.method == 'Bar':
             kernel = getattr(self, 'bar_kernel', 'resident')
             return False if kernel == 'resident' else kernel
+        if self.method == 'RAYEN' and getattr(self, 'wide_backward', 'products') != 'products':
+            return getattr(self, 'wide_kernel', 'products') + '+bwd_' + self.wide_backward
         if self.method == 'RAYEN' and getattr(self, 'wide_kernel', 'products') != 'products':
             return self.wide_kernel          # (method 'RAYEN' has no old head)
         return bool(old_head)
@@ -84,9 +87,10 @@ class ConstraintModule(torch.nn.Module):
 
     BAR_KERNELS = ('resident', 'stream', 'auto')
     WIDE_KERNELS = ops.WIDE_KERNELS
+    WIDE_BACKWARDS = ops.WIDE_BACKWARDS
 
     def __init__(self, cs, input_dim=None, method='RAYEN', create_map=True, args_DC3=None, *, bar_kernel='resident',
-                 bar_window_bytes=0, wide_kernel='products'):
+                 bar_window_bytes=0, wide_kernel='products', wide_backward='products'):
         super().__init__()
 
         self.method = method
@@ -97,9 +101,18 @@ class ConstraintModule(torch.nn.Module):
         # method='RAYEN' on wide sets (n beyond the register-resident kernels, ops._WIDE_MIN_N): 'products' (the default: a
         # library GEMM and rayen_wide.hip over its products) or 'fused' (rayen_wide_fused.hip: one launch, no products
         # matrix; fp32, no LMI, n <= 1024 -- anything else takes the module's loud path).  No effect on narrower sets.  The
-        # backward runs on the products route either way.  There is no 'auto': both serve the same sets, and no timing
+        # backward is chosen by `wide_backward` below (the products route by default).  There is no 'auto': both serve the same sets, and no timing
         # enters a dispatch here.
         self.wide_kernel = wide_kernel
+        if wide_backward not in self.WIDE_BACKWARDS:
+            raise ValueError(f"wide_backward must be one of {self.WIDE_BACKWARDS}, got {wide_backward!r}")
+        if wide_backward != 'products' and method != 'RAYEN':
+            raise ValueError(f"wide_backward={wide_backward!r} chooses a kernel of method 'RAYEN'; this module's method is {method!r}")
+        # the backward of the same sets, chosen independently (it consumes kappa and active of whichever forward made them):
+        # 'products' (the default: two library GEMMs around the coefficient kernel of rayen_wide.hip) or 'fused'
+        # (rayen_wide_fused_bwd.hip: one launch over the active constraints' rows; fp32, no LMI, n <= 1024 -- anything else
+        # takes the backward's loud path, ops._bwd_or_detour).  No 'auto' here either.
+        self.wide_backward = wide_backward
         if bar_kernel not in self.BAR_KERNELS:
             raise ValueError(f"bar_kernel must be one of {self.BAR_KERNELS}, got {bar_kernel!r}")
         if bar_kernel != 'resident' and method != 'Bar':
@@ -304,6 +317,7 @@ class ConstraintModule(torch.nn.Module):
         self.__dict__.setdefault("bar_kernel", 'resident')       # (pickles from before the streamed Bar kernels)
         self.__dict__.setdefault("bar_window_bytes", 0)
         self.__dict__.setdefault("wide_kernel", 'products')      # (pickles from before the fused wide forward)
+        self.__dict__.setdefault("wide_backward", 'products')    # (pickles from before the fused wide backward)
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
                                  'UU': self.forwardForUU, 'Bar': self.forwardForBar,
                                  'DC3': self.forwardForDC3}[self.method]
@@ -331,7 +345,10 @@ class ConstraintModule(torch.nn.Module):
                 y, _, _ = ops.project_raw(v, dp, want_active=False, old_head=old_head, want_kappa=False,
                                           wide_kernel='fused' if fused else 'products')
                 return y, None
-            if fused:
+            if not old_head and getattr(self, "wide_backward", 'products') != 'products':
+                y, kappa, _ = torch.ops.rayen_amd.ray_project_wide(v, pack_id, need_active, 'fused' if fused else 'products',
+                                                                   self.wide_backward)
+            elif fused:
                 y, kappa, _ = torch.ops.rayen_amd.ray_project_wide_fused(v, pack_id, need_active)
             else:
                 y, kappa, _ = torch.ops.rayen_amd.ray_project(v, pack_id, need_active, old_head)

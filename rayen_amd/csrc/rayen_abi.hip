@@ -819,6 +819,7 @@ void rayen_pack_destroy(RayenPack* p) {
   if (p->ws8_32) mfma_pair_ws8_free(p->ws8_32);
   if (p->wide) wide_free(p->wide);
   if (p->wf32) wide_fused_free(p->wf32);
+  if (p->wfb32) wide_fused_bwd_free(p->wfb32);
   if (p->q32) lmi_quad_free(p->q32);
   if (p->w32) lmi_wave_free(p->w32);
   if (p->w64) lmi_wave_free(p->w64);
@@ -918,6 +919,26 @@ int rayen_ray_project_wide_fused_f32(const RayenPack* p, const float* v, int64_t
   if (rc) return rc;
   g_last_forward = RAYEN_KERNEL_WIDE_FUSED;
   return wide_fused_forward(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
+}
+
+int rayen_wide_fused_bwd_served(const RayenPack* p, int32_t f64) {
+  return (p != nullptr && !f64 && wide_fused_bwd_served(p)) ? 1 : 0;
+}
+
+int64_t rayen_wide_fused_bwd_workspace_bytes(const RayenPack* p, int64_t B) {
+  return (p == nullptr || B <= 0) ? 0 : wide_fused_bwd_workspace_bytes(p, B);
+}
+
+int rayen_ray_project_wide_fused_bwd_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, const float* kappa,
+                                         const int32_t* active, const float* grad_y, int64_t ldg, float* grad_v, int64_t ldgv,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  if (p == nullptr || B < 0 || ldv < p->n || ldg < p->k || ldgv < p->n) return RAYEN_E_BAD_ARG;
+  if (B > 0 && (!v || !kappa || !active || !grad_y || !grad_v)) return RAYEN_E_BAD_ARG;
+  if (B > ((int64_t)1 << 31) - 32) return RAYEN_E_BAD_ARG;
+  const int rc = check_ready<float>(p, false);
+  if (rc) return rc;
+  return wide_fused_backward(p, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, workspace, workspace_bytes,
+                             static_cast<hipStream_t>(stream));
 }
 
 static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy,

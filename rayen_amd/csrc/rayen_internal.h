@@ -63,13 +63,14 @@ struct SplitImage;      // rayen_mfma_split.hip
 struct PairImage;       // rayen_pair_image.h
 struct Ws8Image;        // rayen_mfma_pair_ws8.hip
 struct WideImage;       // rayen_wide.hip
-struct WideFusedImage;  // rayen_wide_fused.hip
+struct WideFusedImage;  // rayen_wide_fused_common.h
+struct WideFusedBwdImage;  // rayen_wide_fused_bwd.hip
 
 }  // namespace rayen
 
 // Immutable after rayen_pack_create returns (every device image is built there), so it is shared by threads and
-// streams without a lock -- but for `wf32`, the image of the opt-in fused wide forward, which its first call builds under
-// a lock of its own (rayen_wide_fused.hip).
+// streams without a lock -- but for `wf32` and `wfb32`, the images of the opt-in fused wide forward and backward, which their
+// first calls build under a lock of their own (rayen_wide_fused_common.h).
 struct RayenPack {
   int device = -1;
   int k = 0, n = 0, n_rows = 0;
@@ -110,6 +111,9 @@ struct RayenPack {
   // route is asked for (state 0: not asked yet | 1: built | 2: the route does not serve the pack)
   mutable rayen::WideFusedImage* wf32 = nullptr;
   mutable int wf32_state = 0;
+  // the fused wide backward's images, lazy in the same way and under the same lock (it shares wf32's W where that exists)
+  mutable rayen::WideFusedBwdImage* wfb32 = nullptr;
+  mutable int wfb32_state = 0;
   double check_split = -1.0, check_exact = -1.0, check_pair = -1.0;  // worst row errors against fp64 (fp32_selfcheck)
   // [linear rows, quadratics, cones] + ONE LMI the lane kernels do not hold: the lane kernel evaluates everything but the
   // LMI (generic image built with skip_lmi), the workgroup-per-sample kernel the LMI on top of that (rayen_abi.hip)
@@ -136,6 +140,14 @@ bool wide_fused_served(const RayenPack* p);
 void wide_fused_free(WideFusedImage* img);
 int wide_fused_forward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy, float* kappa,
                        int32_t* active, int32_t* nan_flag, hipStream_t stream);
+
+// their backward without T and C (rayen_wide_fused_bwd.hip): fp32, no LMI, n <= 1024, its tiles within LDS
+bool wide_fused_bwd_served(const RayenPack* p);
+int64_t wide_fused_bwd_workspace_bytes(const RayenPack* p, int64_t B);
+void wide_fused_bwd_free(WideFusedBwdImage* img);
+int wide_fused_backward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, const float* kappa, const int32_t* active,
+                        const float* grad_y, int64_t ldg, float* grad_v, int64_t ldgv, void* workspace, int64_t workspace_bytes,
+                        hipStream_t stream);
 
 // SIMDs the persistent grids may fill: all of the device's minus rayen_reserve_cus() compute units (a collective that
 // runs beside the projection -- RCCL's all-gather kernels in the multi-GPU step -- needs CUs of its own)

@@ -258,11 +258,23 @@ def _(v, pack_id, need_active):
             v.new_empty((B if need_active else 0, 2), dtype=torch.int32))
 
 
-def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=False, bucketed=True):
+WIDE_BACKWARDS = ('products', 'fused')
+
+
+def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=False, bucketed=True,
+                 wide_backward='products', group=True):
     """Direct call of the backward entry points; ``force_generic`` pins the lane-per-sample kernel
     where ``rayen_ray_project_bwd_f32/_f64`` would pick the matrix-core one.  ``bucketed``: hand the library the
     scratch buffer it asks for (``rayen_bwd_workspace_bytes_f32``) so that it may group the samples by active
-    constraint and walk only that constraint's tiles; ``False`` pins the plain walk (same results)."""
+    constraint and walk only that constraint's tiles; ``False`` pins the plain walk (same results).
+    ``wide_backward``: what serves a call that takes the wide route (``_wide_route``): ``'products'`` -- two library GEMMs
+    around the coefficient kernel of rayen_wide.hip -- or ``'fused'`` -- ``rayen_ray_project_wide_fused_bwd_f32``
+    (rayen_wide_fused_bwd.hip): one launch over the active constraints' rows, neither T nor C; fp32, no LMI, n <= 1024,
+    anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on a call that does not take the wide route.  ``group``
+    (developer flag of the fused route): hand the library the workspace with which it groups the rows by active constraint;
+    ``False`` pins batch order (same bits)."""
+    if wide_backward not in WIDE_BACKWARDS:
+        raise ValueError(f"wide_backward must be one of {WIDE_BACKWARDS}, got {wide_backward!r}")
     _check_input(v, pack)
     v = _dense_rows(v, pack.consts.n + (1 if old_head else 0))
     grad_y = grad_y.contiguous()
@@ -276,6 +288,19 @@ def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=F
             raise RuntimeError("force_generic selects between the two RAYEN backward kernels only")
         name = "rayen_ray_project_bwd_generic_f32" if v.dtype == torch.float32 else "rayen_ray_project_bwd_generic_f64"
     Wt = _wide_route(v, pack, force_generic, old_head) if B else None
+    if Wt is not None and wide_backward == 'fused':
+        with _on_device(v.device):
+            if v.dtype != torch.float32:
+                code = _lib.E_UNSUPPORTED        # (the fused kernel is fp32 only: rayen_wide_fused_bwd_served(pack, 1) == 0)
+            else:
+                lib = _lib.load()
+                ws_bytes = int(lib.rayen_wide_fused_bwd_workspace_bytes(pack.handle, B)) if group else 0
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device) if ws_bytes > 0 else None   # (caching allocator)
+                code = lib.rayen_ray_project_wide_fused_bwd_f32(
+                    pack.handle, _ptr(v), B, v.stride(0), _ptr(kappa), _ptr(active), _ptr(grad_y), grad_y.stride(0),
+                    _ptr(grad_v), grad_v.stride(0), _ptr(ws), ws_bytes, _stream(v.device.index))
+        _lib.check(code, "rayen_ray_project_wide_fused_bwd")
+        return grad_v
     if Wt is not None:
         # wide sets: T = v W_ext' again (one GEMM), the coefficient kernel, grad_v = C W_ext (+ s g): rayen_wide.hip
         n, k = pack.consts.n, pack.consts.k
@@ -319,21 +344,30 @@ def ray_project_bwd(v: torch.Tensor, kappa: torch.Tensor, active: torch.Tensor,
     return backward_raw(v, kappa, active, grad_y, _pack(pack_id), old_head)
 
 
-def _bwd_or_detour(v, kappa, active, grad_y, pack_id, old_head):
+def _bwd_or_detour(v, kappa, active, grad_y, pack_id, old_head, wide_backward='products'):
     """The HIP backward; where the kernels decline the shape (``RAYEN_E_UNSUPPORTED``), autograd through the packed
-    torch evaluator on the same device -- loudly, once per pack.  Called from the autograd formulas (NOT from inside the
-    custom op: below the dispatcher's autograd key nothing would be recorded)."""
+    torch evaluator on the same device -- loudly, once per pack and route.  Called from the autograd formulas (NOT from
+    inside the custom op: below the dispatcher's autograd key nothing would be recorded).  A refusal of
+    ``wide_backward='fused'`` is remembered per dtype: later calls go to the evaluator without asking again."""
+    fused = wide_backward == 'fused'
+    if fused and (v.dtype, 'fused') in _pack(pack_id).__dict__.get("_refused_bwd", ()):
+        return _eager_backward(_pack(pack_id), v, grad_y, old_head)
     try:
+        if fused:
+            return torch.ops.rayen_amd.ray_project_bwd_wide_fused(v, kappa, active, grad_y, pack_id)
         return torch.ops.rayen_amd.ray_project_bwd(v, kappa, active, grad_y, pack_id, old_head)
     except _lib.RayenError as err:
         if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
             raise
         pack = _pack(pack_id)
-        if not pack.__dict__.get("_warned_bwd"):
+        warned = "_warned_bwd_wide_fused" if fused else "_warned_bwd"
+        if not pack.__dict__.get(warned):
             warnings.warn(f"rayen_amd: no HIP backward kernel serves this constraint set ({err}); gradients come from "
                           "autograd through the packed torch evaluator (rayen_amd/eager.py) on " + str(v.device),
                           RuntimeWarning, stacklevel=2)
-            pack.__dict__["_warned_bwd"] = True
+            pack.__dict__[warned] = True
+        if fused:
+            pack.__dict__.setdefault("_refused_bwd", set()).add((v.dtype, 'fused'))
         return _eager_backward(pack, v, grad_y, old_head)
 
 
@@ -386,6 +420,57 @@ def _wide_fused_backward(ctx, grad_y, grad_kappa, grad_active):
 
 
 ray_project_wide_fused.register_autograd(_wide_fused_backward, setup_context=_wide_fused_setup_context)
+
+
+@torch.library.custom_op("rayen_amd::ray_project_bwd_wide_fused", mutates_args=())
+def ray_project_bwd_wide_fused(v: torch.Tensor, kappa: torch.Tensor, active: torch.Tensor, grad_y: torch.Tensor,
+                               pack_id: int) -> torch.Tensor:
+    """``rayen_amd::ray_project_bwd`` with ``wide_backward='fused'``: wide sets on rayen_wide_fused_bwd.hip (a call that
+    does not take the wide route runs what ``ray_project_bwd`` runs)."""
+    return backward_raw(v, kappa, active, grad_y, _pack(pack_id), wide_backward='fused')
+
+
+@ray_project_bwd_wide_fused.register_fake
+def _(v, kappa, active, grad_y, pack_id):
+    return torch.empty_like(v)
+
+
+@torch.library.custom_op("rayen_amd::ray_project_wide", mutates_args=())
+def ray_project_wide(v: torch.Tensor, pack_id: int, need_active: bool, wide_kernel: str,
+                     wide_backward: str) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rayen_amd::ray_project`` with both choices of the wide route spelled out: the forward by ``wide_kernel``, the
+    backward (``rayen_amd::ray_project_bwd`` or ``rayen_amd::ray_project_bwd_wide_fused``) by ``wide_backward`` -- it consumes
+    ``kappa`` and ``active`` of whichever forward made them."""
+    if wide_backward not in WIDE_BACKWARDS:
+        raise ValueError(f"wide_backward must be one of {WIDE_BACKWARDS}, got {wide_backward!r}")
+    y, kappa, active = project_raw(v, _pack(pack_id), want_active=need_active, wide_kernel=wide_kernel)
+    if active is None:
+        active = torch.empty((0, 2), dtype=torch.int32, device=v.device)
+    return y, kappa, active
+
+
+@ray_project_wide.register_fake
+def _(v, pack_id, need_active, wide_kernel, wide_backward):
+    pack = _pack(pack_id)
+    B = v.shape[0]
+    return (v.new_empty((B, pack.consts.k)), v.new_empty((B,)),
+            v.new_empty((B if need_active else 0, 2), dtype=torch.int32))
+
+
+def _wide_setup_context(ctx, inputs, output):
+    v, pack_id, need_active, _, wide_backward = inputs
+    _setup_context(ctx, (v, pack_id, need_active, False), output)
+    ctx.wide_backward = wide_backward
+
+
+def _wide_backward(ctx, grad_y, grad_kappa, grad_active):
+    v, kappa, active = ctx.saved_tensors
+    if grad_y is None:
+        return torch.zeros_like(v), None, None, None, None
+    return (_bwd_or_detour(v, kappa, active, grad_y, ctx.pack_id, False, ctx.wide_backward), None, None, None, None)
+
+
+ray_project_wide.register_autograd(_wide_backward, setup_context=_wide_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------
