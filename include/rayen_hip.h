@@ -422,6 +422,11 @@ int rayen_dc3_backward_f64(const RayenDc3Pack* pack, const double* q, int64_t B,
  * EXPORTS_DC3_TILE and links it from plain C). */
 #include "rayen_hip_dc3_tile.h"
 
+/* Their fp64 twins on the fp64 matrix cores (additive to ABI v15, six symbols rayen_dc3_tile64_*) are declared, with their
+ * contract, in rayen_hip_dc3_tile64.h, which is part of this header too (tests/test_dc3_tile64_host.py holds it against the
+ * binding's EXPORTS_DC3_TILE64 and links it from plain C). */
+#include "rayen_hip_dc3_tile64.h"
+
 /* ---- Euclidean projection onto the set (ABI v11): the core of the reference's PP / UP layers
  * (rayen/constraint_module.py:76-96 and :488-504), batched and differentiable
  *

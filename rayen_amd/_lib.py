@@ -47,6 +47,10 @@ EXPORTS_TILE = ("rayen_proj_tile_layout", "rayen_proj_tile_served", "rayen_proj_
 # tests/test_dc3_tile_host.py holds the two against each other
 EXPORTS_DC3_TILE = ("rayen_dc3_tile_shape_served", "rayen_dc3_tile_pack_set", "rayen_dc3_tile_served",
                     "rayen_dc3_tile_workspace_bytes", "rayen_dc3_tile_forward_f32", "rayen_dc3_tile_backward_f32")
+# additive to ABI v15, declared in include/rayen_hip_dc3_tile64.h (which rayen_hip.h includes): the fp64 twins of the six
+# above; tests/test_dc3_tile64_host.py holds the two against each other
+EXPORTS_DC3_TILE64 = ("rayen_dc3_tile64_shape_served", "rayen_dc3_tile64_pack_set", "rayen_dc3_tile64_served",
+                      "rayen_dc3_tile64_workspace_bytes", "rayen_dc3_tile64_forward_f64", "rayen_dc3_tile64_backward_f64")
 # additive to ABI v15, declared in include/rayen_hip_cost_stream.h (which rayen_hip.h includes, like the two above);
 # tests/test_cost_stream_host.py holds the two against each other
 EXPORTS_COST_STREAM = ("rayen_cost_stream_set", "rayen_cost_stream_served", "rayen_soft_cost_stream_f32",
@@ -231,6 +235,18 @@ def load():
     lib.rayen_dc3_tile_forward_f32.argtypes = [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]
     lib.rayen_dc3_tile_backward_f32.restype = ctypes.c_int
     lib.rayen_dc3_tile_backward_f32.argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
+    lib.rayen_dc3_tile64_shape_served.restype = ctypes.c_int
+    lib.rayen_dc3_tile64_shape_served.argtypes = [i32, i32, i32, i32]
+    lib.rayen_dc3_tile64_pack_set.restype = ctypes.c_int
+    lib.rayen_dc3_tile64_pack_set.argtypes = [p, p, p, p, p, p, p, p]
+    lib.rayen_dc3_tile64_served.restype = ctypes.c_int
+    lib.rayen_dc3_tile64_served.argtypes = [p]
+    lib.rayen_dc3_tile64_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_dc3_tile64_workspace_bytes.argtypes = [p, i64, i32, i32]
+    lib.rayen_dc3_tile64_forward_f64.restype = ctypes.c_int
+    lib.rayen_dc3_tile64_forward_f64.argtypes = [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]
+    lib.rayen_dc3_tile64_backward_f64.restype = ctypes.c_int
+    lib.rayen_dc3_tile64_backward_f64.argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
     lib.rayen_proj_pack_create.restype = ctypes.c_int
     lib.rayen_proj_pack_create.argtypes = [p, p, p, p, i32, i32, i32, p, i32, f64, f64, f64, ctypes.POINTER(ctypes.c_void_p)]
     lib.rayen_proj_pack_set_psd.restype = ctypes.c_int

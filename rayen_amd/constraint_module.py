@@ -21,8 +21,8 @@ vertices and rays once (``rayen_amd/vrep.py``, no cddlib) and runs one HIP kerne
 (``rayen_amd/csrc/rayen_bar.hip``, or with the keyword ``bar_kernel='stream' | 'auto'`` ``rayen_bar_stream.hip``, which
 needs no LDS proportional to the number of generators); ``'DC3'`` (completion + gradient correction, :134-228 and :265-336, linear and
 quadratic sets only) needs ``args_DC3`` and runs its fixed iteration, batch-global stop included, on
-``rayen_amd/csrc/rayen_dc3.hip`` or, with ``args_DC3['kernel'] = 'tile' | 'auto'``, ``rayen_dc3_tile.hip`` (host side:
-``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
+``rayen_amd/csrc/rayen_dc3.hip`` or, with ``args_DC3['kernel'] = 'tile' | 'auto'``, ``rayen_dc3_tile.hip`` (fp32 input) or
+``rayen_dc3_tile64.hip`` (fp64 input) (host side: ``rayen_amd/dc3.py``).  The other paper baselines (``UP, PP``) raise
 ``NotImplementedError`` here: they are served by a module of their own, ``rayen_amd.projection.ProjectionModule``.
 
 Documented deviation: for an SOC whose ray never meets the cone (negative
@@ -471,6 +471,7 @@ class ConstraintModule(torch.nn.Module):
             entry = packs[index] = (dp, ops.register_pack(dp))
             # what 'tile' / 'auto' need from the device is settled here, with the pack's own uploads (like them, not while
             # a stream is capturing): the calls after the first only look the answers up
+            # (under 'tile' the fp64 image waits for the first fp64 call: that call must precede a capture)
             kernel = self.dc3_kernel
             if kernel == 'tile':
                 dp.tile_images()
@@ -481,21 +482,26 @@ class ConstraintModule(torch.nn.Module):
 
     @property
     def dc3_kernel(self):
-        """What ``args_DC3['kernel']`` asks for: ``'lane'`` (the default, rayen_dc3.hip), ``'tile'`` (rayen_dc3_tile.hip)
-        or ``'auto'``."""
+        """What ``args_DC3['kernel']`` asks for: ``'lane'`` (the default, rayen_dc3.hip), ``'tile'`` (rayen_dc3_tile.hip
+        for fp32 input, rayen_dc3_tile64.hip for fp64 input) or ``'auto'``."""
         return _dc3.kernel_choice(self.args_DC3)
 
     def _dc3_kernel_for(self, dp, dtype):
-        """The kernel a call at ``dtype`` runs.  ``'auto'``: the lane kernel wherever it serves the pack at ``dtype``, else
-        the tile kernel where it does (fp32), else the lane kernel, whose refusal is then the one reported.  No timing
-        enters the choice."""
+        """The kernel of ``ops`` a call at ``dtype`` runs.  ``'tile'``: the tile kernel of that dtype (``'tile'`` in fp32,
+        ``'tile64'`` in fp64).  ``'auto'``: the lane kernel wherever it serves the pack at ``dtype``, else the tile kernel
+        of that dtype where it does, else the lane kernel, whose refusal is then the one reported.  No timing enters the
+        choice."""
         kernel = self.dc3_kernel
+        if kernel == 'tile':
+            return 'tile64' if dtype == torch.float64 else 'tile'
         if kernel != 'auto':
             return kernel
         if ops.dc3_lane_served(dp, dtype):
             return 'lane'
         if dtype == torch.float32 and ops.dc3_tile_served(dp):
             return 'tile'
+        if dtype == torch.float64 and ops.dc3_tile64_served(dp):
+            return 'tile64'
         return 'lane'
 
     def obtainyoFromypDC3(self, yp):
@@ -526,6 +532,8 @@ class ConstraintModule(torch.nn.Module):
                 y, steps = ops.dc3_forward_raw(q2, dp, lr, momentum, eps, limit, kernel)      # plain inference: straight to the C ABI
             elif kernel == 'tile':
                 y, steps = torch.ops.rayen_amd.dc3_project_tile(q2, pack_id, lr, momentum, eps, limit)
+            elif kernel == 'tile64':
+                y, steps = torch.ops.rayen_amd.dc3_project_tile64(q2, pack_id, lr, momentum, eps, limit)
             else:
                 y, steps = torch.ops.rayen_amd.dc3_project(q2, pack_id, lr, momentum, eps, limit)
         except _lib.RayenError as err:

@@ -591,6 +591,7 @@ void rayen_dc3_pack_destroy(RayenDc3Pack* p) {
     if (p->img64) (void)hipFree(p->img64);
     if (p->perm) (void)hipFree(p->perm);
     if (p->tile_img) (void)hipFree(p->tile_img);
+    if (p->tile_img64) (void)hipFree(p->tile_img64);
   }
   delete p;
 }

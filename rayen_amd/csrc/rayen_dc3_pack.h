@@ -13,4 +13,5 @@ struct RayenDc3Pack {
   double* img64 = nullptr;
   int32_t* perm = nullptr;      // [n] partial variables, then [no] other variables
   float* tile_img = nullptr;    // rayen_dc3_tile_image.h (fp32 only)
+  double* tile_img64 = nullptr; // rayen_dc3_tile64_image.h (fp64 only; rayen_dc3_tile64_pack_set, likewise on request)
 };

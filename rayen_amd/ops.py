@@ -619,13 +619,14 @@ def _host_ptr(x):
 
 def _workspace(pack, t, backward, max_steps=None, tile=False):
     """``(scratch tensor, its size for the library)`` of a DC3 call (``max_steps`` given) or a projection call on the rows
-    of ``t``, as ``rayen_*_workspace_bytes`` sizes it; refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read here, at
-    call time)."""
+    of ``t``, as ``rayen_*_workspace_bytes`` sizes it (``tile``: false for the lane / wave kernels, else true or, for a DC3
+    call, the tile kernel's name, ``'tile'`` or ``'tile64'``); refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read
+    here, at call time)."""
     B, f64 = t.shape[0], int(t.dtype == torch.float64)
     if max_steps is not None:
         limit, extra = DC3_MAX_WORKSPACE_BYTES, 0
         if tile:
-            name = "rayen_dc3_tile_workspace_bytes"
+            name = "rayen_dc3_tile64_workspace_bytes" if tile == "tile64" else "rayen_dc3_tile_workspace_bytes"
             nbytes = int(_entry(name)(pack.handle, B, int(max_steps), int(backward)))
         else:
             name = "rayen_dc3_workspace_bytes"
@@ -818,9 +819,10 @@ DC3_MAX_WORKSPACE_BYTES = 8 << 30
 
 class Dc3Pack(_SidePack):
     """Owner of one ``RayenDc3Pack*``: fp32 and fp64 images of the effective forms (``rayen_amd/dc3.py::pack_arrays``) on one
-    device, plus the NaN flag its forward raises.  The tile kernels' image (rayen_dc3_tile.hip) is uploaded on the first
-    call that asks for ``kernel='tile'``: a user who never does allocates nothing for it on the device.  Until then the
-    pack keeps a reference to the host arrays it was built from (no copy; released once the image is up)."""
+    device, plus the NaN flag its forward raises.  The tile kernels' images (fp32: rayen_dc3_tile.hip, fp64:
+    rayen_dc3_tile64.hip) are uploaded each on the first call that asks for ``kernel='tile'`` / ``'tile64'``: a user who
+    never does allocates nothing for them on the device.  Until both are settled the pack keeps a reference to the host
+    arrays it was built from (no copy; released once both images are up)."""
     _layer = "dc3"
 
     def __init__(self, arrays, device_index):
@@ -831,33 +833,48 @@ class Dc3Pack(_SidePack):
                      ptr(a["re"]), int(a["Pe"].shape[0]), ptr(a["C"]), ptr(a["c0"]), ptr(a["partial"]), ptr(a["other"]),
                      self.n, self.k)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=f"cuda:{self.device_index}")
-        self._arrays = arrays      # the host arrays: what rayen_dc3_tile_pack_set reads, should it ever be called
-        self._tile_set = False
+        self._arrays = arrays      # the host arrays: what rayen_dc3_tile*_pack_set read, should they ever be called
+        self._tile_set = set()     # of "rayen_dc3_tile_pack_set" / "rayen_dc3_tile64_pack_set": the uploads settled
         self._lane_served = {}
 
-    def tile_images(self):
-        """Upload the tile kernels' image (once; not while a stream is capturing)."""
-        if not self._tile_set:
+    def _tile_image(self, setter):
+        if setter not in self._tile_set:
             a, ptr = self._arrays, _host_ptr
             with torch.cuda.device(self.device_index):
-                _lib.check(_entry("rayen_dc3_tile_pack_set")(self.handle, ptr(a["A1e"]), ptr(a["b1e"]), ptr(a["Pe"]),
-                                                             ptr(a["qe"]), ptr(a["re"]), ptr(a["C"]), ptr(a["c0"])),
-                           "rayen_dc3_tile_pack_set")
-            self._tile_set = True
-            self._arrays = None
+                _lib.check(_entry(setter)(self.handle, ptr(a["A1e"]), ptr(a["b1e"]), ptr(a["Pe"]), ptr(a["qe"]),
+                                          ptr(a["re"]), ptr(a["C"]), ptr(a["c0"])), setter)
+            self._tile_set.add(setter)
+            if len(self._tile_set) == 2:
+                self._arrays = None
+
+    def tile_images(self):
+        """Upload the fp32 tile kernels' image (once; not while a stream is capturing)."""
+        self._tile_image("rayen_dc3_tile_pack_set")
+
+    def tile64_images(self):
+        """Upload the fp64 tile kernels' image (once; not while a stream is capturing)."""
+        self._tile_image("rayen_dc3_tile64_pack_set")
 
 
-DC3_KERNELS = ("lane", "tile")
+DC3_KERNELS = ("lane", "tile")                  # the kernels that take fp32 input
+DC3_KERNELS_F64 = ("lane", "tile64")            # ... and fp64 input ('tile64' is not in DC3_KERNELS: it refuses fp32)
+_DC3_KERNEL_NAMES = ("lane", "tile", "tile64")
 
 
 def _dc3_entry(direction, kernel, dtype, pack):
     """The library entry of ``kernel``: ``'lane'`` is rayen_dc3.hip (one lane per row, the image in LDS), ``'tile'``
     rayen_dc3_tile.hip (32 rows per workgroup on the matrix cores; fp32 only: an fp64 call is refused with
-    ``E_UNSUPPORTED``)."""
-    if kernel not in DC3_KERNELS:
-        raise ValueError(f"kernel must be one of {DC3_KERNELS}, got {kernel!r}")
+    ``E_UNSUPPORTED``), ``'tile64'`` rayen_dc3_tile64.hip (16 rows per workgroup on the fp64 matrix cores; fp64 only: an
+    fp32 call is refused with ``E_UNSUPPORTED``)."""
+    if kernel not in _DC3_KERNEL_NAMES:
+        raise ValueError(f"kernel must be one of {_DC3_KERNEL_NAMES}, got {kernel!r}")
     if kernel == "lane":
         return _typed(f"rayen_dc3_{direction}", dtype)
+    if kernel == "tile64":
+        if dtype != torch.float64:
+            raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_dc3_tile64_{direction}")
+        pack.tile64_images()
+        return _entry(f"rayen_dc3_tile64_{direction}_f64")
     if dtype != torch.float32:
         raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_dc3_tile_{direction}")
     pack.tile_images()
@@ -865,8 +882,8 @@ def _dc3_entry(direction, kernel, dtype, pack):
 
 
 def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps, kernel='lane'):
-    """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*`` (``kernel='tile'``: ``rayen_dc3_tile_forward_f32``);
-    ``steps`` is the batch-global number of steps."""
+    """``(y [B, k], steps [1] int32)`` through ``rayen_dc3_forward_*`` (``kernel='tile'``: ``rayen_dc3_tile_forward_f32``;
+    ``kernel='tile64'``: ``rayen_dc3_tile64_forward_f64``); ``steps`` is the batch-global number of steps."""
     _check_rows(q, pack.n, pack, "q", "dc3")
     entry = _dc3_entry("forward", kernel, q.dtype, pack)
     q = _dense_rows(q, pack.n)
@@ -878,7 +895,7 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps, kernel='lane'):
     y = torch.empty((B, pack.k), dtype=q.dtype, device=q.device)
     steps = torch.empty((1,), dtype=torch.int32, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, False, max_steps, tile=kernel == "tile")
+        ws, nbytes = _workspace(pack, q, False, max_steps, tile=kernel != "lane" and kernel)
         code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(y), pack.k, float(lr), float(momentum),
             float(eps), int(max_steps), _ptr(steps), _ptr(ws), nbytes, _ptr(pack.nan_flag), _stream(q.device.index))
@@ -888,7 +905,8 @@ def dc3_forward_raw(q, pack, lr, momentum, eps, max_steps, kernel='lane'):
 
 def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps, kernel='lane'):
     """``grad_q`` (same shape as ``q``; columns beyond ``n`` are zero) through ``rayen_dc3_backward_*`` (``kernel='tile'``:
-    ``rayen_dc3_tile_backward_f32``); ``steps`` may come from either kernel's forward."""
+    ``rayen_dc3_tile_backward_f32``; ``kernel='tile64'``: ``rayen_dc3_tile64_backward_f64``); ``steps`` may come from any
+    kernel's forward at the same precision."""
     _check_rows(q, pack.n, pack, "q", "dc3")
     entry = _dc3_entry("backward", kernel, q.dtype, pack)
     q = _dense_rows(q, pack.n)
@@ -897,7 +915,7 @@ def dc3_backward_raw(q, steps, grad_y, pack, lr, momentum, max_steps, kernel='la
     grad_q = torch.empty((B, q.shape[1]), dtype=q.dtype, device=q.device) if q.shape[1] == pack.n else \
         torch.zeros((B, q.shape[1]), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, True, max_steps, tile=kernel == "tile")
+        ws, nbytes = _workspace(pack, q, True, max_steps, tile=kernel != "lane" and kernel)
         code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(grad_y), pack.k, _ptr(grad_q),
             grad_q.stride(0) if B else pack.n, float(lr), float(momentum), int(max_steps), _ptr(steps), _ptr(ws), nbytes,
@@ -927,6 +945,13 @@ def dc3_tile_served(pack):
     tile image on first use (an allocation and a copy: not while a stream is capturing)."""
     pack.tile_images()
     return bool(_entry("rayen_dc3_tile_served")(pack.handle))
+
+
+def dc3_tile64_served(pack):
+    """Does the fp64 tile kernel serve this pack (its envelope: ``dc3_tile64_served()`` in rayen_dc3_tile64_image.h)?
+    Uploads the fp64 tile image on first use (an allocation and a copy: not while a stream is capturing)."""
+    pack.tile64_images()
+    return bool(_entry("rayen_dc3_tile64_served")(pack.handle))
 
 
 @torch.library.custom_op("rayen_amd::dc3_project", mutates_args=())
@@ -1003,6 +1028,41 @@ def _dc3_tile_backward(ctx, grad_y, grad_steps):
 
 
 dc3_project_tile.register_autograd(_dc3_tile_backward, setup_context=_dc3_setup_context)
+
+
+@torch.library.custom_op("rayen_amd::dc3_project_tile64", mutates_args=())
+def dc3_project_tile64(q: torch.Tensor, pack_id: int, lr: float, momentum: float, eps: float,
+                       max_steps: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``dc3_project`` in fp64 on the fp64 tile kernel (rayen_dc3_tile64.hip)."""
+    return dc3_forward_raw(q, _pack(pack_id), lr, momentum, eps, max_steps, kernel="tile64")
+
+
+@dc3_project_tile64.register_fake
+def _(q, pack_id, lr, momentum, eps, max_steps):
+    pack = _pack(pack_id)
+    return q.new_empty((q.shape[0], pack.k)), q.new_empty((1,), dtype=torch.int32)
+
+
+@torch.library.custom_op("rayen_amd::dc3_project_tile64_bwd", mutates_args=())
+def dc3_project_tile64_bwd(q: torch.Tensor, steps: torch.Tensor, grad_y: torch.Tensor, pack_id: int, lr: float,
+                           momentum: float, max_steps: int) -> torch.Tensor:
+    return dc3_backward_raw(q, steps, grad_y, _pack(pack_id), lr, momentum, max_steps, kernel="tile64")
+
+
+@dc3_project_tile64_bwd.register_fake
+def _(q, steps, grad_y, pack_id, lr, momentum, max_steps):
+    return torch.empty_like(q)
+
+
+def _dc3_tile64_backward(ctx, grad_y, grad_steps):
+    q, steps = ctx.saved_tensors
+    if grad_y is None:
+        return None, None, None, None, None, None
+    return (torch.ops.rayen_amd.dc3_project_tile64_bwd(q, steps, grad_y, ctx.pack_id, ctx.lr, ctx.momentum, ctx.max_steps),
+            None, None, None, None, None)
+
+
+dc3_project_tile64.register_autograd(_dc3_tile64_backward, setup_context=_dc3_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------
