@@ -21,8 +21,7 @@ def main(names):
         prog = pr.module_for(name).program
         print(f"{name}: program (n, m, cones) = {(prog.n, prog.m, len(prog.soc_rows))}, rho {prog.rho}, "
               f"kink rows {int(np.count_nonzero(ref.kink))}, mirror iters {int(run.iters.max())} / {run.iters.mean():.0f}")
-        np.savez_compressed(ptc.fixture_path(name), q=ref.q, gy=ref.gy, z=ref.z, grad_q=ref.grad_q, margin=ref.margin,
-                            interior=ref.interior, mirror_z=run.z, mirror_grad_q=run.grad_q, mirror_iters=run.iters)
+        ptc.save_fixture(ptc.fixture_path(name), ref, {"float32": run})
 
 
 if __name__ == "__main__":
