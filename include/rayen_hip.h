@@ -486,6 +486,11 @@ int rayen_proj_backward_f64(const RayenProjPack* pack, const double* g, int64_t 
  * EXPORTS_TILE and links the five from C). */
 #include "rayen_hip_tile.h"
 
+/* Its fp64 twin on tiles of 16 samples on the fp64 matrix cores (rayen_proj_tile64.hip; additive to ABI v15, six symbols
+ * rayen_proj_tile64_*) is declared, with its contract, in rayen_hip_tile64.h, which is part of this header too
+ * (tests/test_proj_tile64_host.py holds it against the binding's EXPORTS_TILE64 and links the six from C). */
+#include "rayen_hip_tile64.h"
+
 /* ---- Soft cost and violation of a batch (ABI v12): the reference's training loss of UU / UP / DC3
  * (examples/cost_computer.py:69-110) and the residual metric every method is judged by, loss AND gradient in one launch
  *

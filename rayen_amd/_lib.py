@@ -43,6 +43,10 @@ EXPORTS = (
 # against each other
 EXPORTS_TILE = ("rayen_proj_tile_layout", "rayen_proj_tile_served", "rayen_proj_tile_workspace_bytes",
                 "rayen_proj_tile_forward_f32", "rayen_proj_tile_backward_f32")
+# additive to ABI v15, declared in include/rayen_hip_tile64.h (which rayen_hip.h includes): the fp64 twins on tiles of 16
+# samples; tests/test_proj_tile64_host.py holds the two against each other
+EXPORTS_TILE64 = ("rayen_proj_tile64_layout", "rayen_proj_tile64_pack_set", "rayen_proj_tile64_served",
+                  "rayen_proj_tile64_workspace_bytes", "rayen_proj_tile64_forward_f64", "rayen_proj_tile64_backward_f64")
 # additive to ABI v15, declared in include/rayen_hip_dc3_tile.h (which rayen_hip.h includes, like rayen_hip_tile.h);
 # tests/test_dc3_tile_host.py holds the two against each other
 EXPORTS_DC3_TILE = ("rayen_dc3_tile_shape_served", "rayen_dc3_tile_pack_set", "rayen_dc3_tile_served",
@@ -271,6 +275,18 @@ def load():
     lib.rayen_proj_tile_forward_f32.argtypes = [p, p, i64, i64, p, i64, i32p, p, f64, i32, p, i64, p]
     lib.rayen_proj_tile_backward_f32.restype = ctypes.c_int
     lib.rayen_proj_tile_backward_f32.argtypes = [p, p, i64, i64, p, i32p, p, i64, f64, i32, p, i64, p]
+    lib.rayen_proj_tile64_layout.restype = ctypes.c_int
+    lib.rayen_proj_tile64_layout.argtypes = [i32, i32, p, i32, i32p, p, p, p]
+    lib.rayen_proj_tile64_pack_set.restype = ctypes.c_int
+    lib.rayen_proj_tile64_pack_set.argtypes = [p, p, p, p, p, p, i32]
+    lib.rayen_proj_tile64_served.restype = ctypes.c_int
+    lib.rayen_proj_tile64_served.argtypes = [p]
+    lib.rayen_proj_tile64_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_proj_tile64_workspace_bytes.argtypes = [p, i64, i32]
+    lib.rayen_proj_tile64_forward_f64.restype = ctypes.c_int
+    lib.rayen_proj_tile64_forward_f64.argtypes = [p, p, i64, i64, p, i64, i32p, p, f64, i32, p, i64, p]
+    lib.rayen_proj_tile64_backward_f64.restype = ctypes.c_int
+    lib.rayen_proj_tile64_backward_f64.argtypes = [p, p, i64, i64, p, i32p, p, i64, f64, i32, p, i64, p]
     lib.rayen_cost_pack_create.restype = ctypes.c_int
     lib.rayen_cost_pack_create.argtypes = [p, p, i32, p, p, p, i32, p, p, p, p, p, i32, p, p, i32, i32,
                                            ctypes.POINTER(ctypes.c_void_p)]

@@ -755,6 +755,7 @@ void rayen_proj_pack_destroy(RayenProjPack* p) {
     if (p->img32) (void)hipFree(p->img32);
     if (p->img64) (void)hipFree(p->img64);
     rayen::proj_tile_destroy(p->tile);
+    rayen::proj_tile64_destroy(p->tile64);
   }
   delete p;
 }

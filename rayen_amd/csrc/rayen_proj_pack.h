@@ -1,6 +1,7 @@
 // RayenProjPack: what rayen_proj.hip (wave per sample, image in LDS) and rayen_proj_tile.hip (32 samples per workgroup
 // on the matrix cores) share.  The wave kernel's fields are filled by rayen_proj_pack_create; the tile kernel's images
-// hang off `tile` (null: the shape is outside tile_served(), or the set has a PSD block).
+// hang off `tile` (null: the shape is outside tile_served(), or the set has a PSD block); the fp64 tile kernel's
+// (rayen_proj_tile64.hip) off `tile64`, uploaded on request by rayen_proj_tile64_pack_set.
 #pragma once
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #include "rayen_side_pack.h"
 
 struct RayenProjTile;
+struct RayenProjTile64;
 
 namespace rayen {
 constexpr int kProjMaxSoc = 32;               // cones the WAVE kernel's argument block holds
@@ -15,6 +17,10 @@ constexpr int kProjMaxSoc = 32;               // cones the WAVE kernel's argumen
 RayenProjTile* proj_tile_create(const double* G, const double* h, const double* Kinv, const double* w0, int n, int m,
                                 int m_lin, const int32_t* soc_rows, int n_soc);
 void proj_tile_destroy(RayenProjTile* t);
+// rayen_proj_tile64.hip: the fp64 tile images of a program (null: not served, or no memory), and their release
+RayenProjTile64* proj_tile64_create(const double* G, const double* h, const double* Kinv, const double* w0, int n, int m,
+                                    int m_lin, const int32_t* soc_rows, int n_soc);
+void proj_tile64_destroy(RayenProjTile64* t);
 }  // namespace rayen
 
 struct RayenProjPack {
@@ -26,4 +32,5 @@ struct RayenProjPack {
   float* img32 = nullptr;
   double* img64 = nullptr;
   RayenProjTile* tile = nullptr;                // the tile kernel's images (fp32 only)
+  RayenProjTile64* tile64 = nullptr;            // the fp64 tile kernel's images (fp64 only; on request)
 };

@@ -619,8 +619,8 @@ def _host_ptr(x):
 
 def _workspace(pack, t, backward, max_steps=None, tile=False):
     """``(scratch tensor, its size for the library)`` of a DC3 call (``max_steps`` given) or a projection call on the rows
-    of ``t``, as ``rayen_*_workspace_bytes`` sizes it (``tile``: false for the lane / wave kernels, else true or, for a DC3
-    call, the tile kernel's name, ``'tile'`` or ``'tile64'``); refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read
+    of ``t``, as ``rayen_*_workspace_bytes`` sizes it (``tile``: false for the lane / wave kernels, else the tile kernel's
+    name, ``'tile'`` or ``'tile64'``); refused beyond the layer's ``*_MAX_WORKSPACE_BYTES`` (read
     here, at call time)."""
     B, f64 = t.shape[0], int(t.dtype == torch.float64)
     if max_steps is not None:
@@ -634,7 +634,7 @@ def _workspace(pack, t, backward, max_steps=None, tile=False):
     else:
         limit, extra = PROJ_MAX_WORKSPACE_BYTES, B * pack.m * t.element_size()   # (v*)
         if tile:
-            name = "rayen_proj_tile_workspace_bytes"
+            name = "rayen_proj_tile64_workspace_bytes" if tile == "tile64" else "rayen_proj_tile_workspace_bytes"
             nbytes = int(_entry(name)(pack.handle, B, int(backward)))
         else:
             name = "rayen_proj_workspace_bytes"
@@ -1074,12 +1074,14 @@ PROJ_MAX_WORKSPACE_BYTES = 8 << 30
 
 
 class ProjPack(_SidePack):
-    """Owner of one ``RayenProjPack*``: fp32 and fp64 images of a ``projection.Program`` on one device."""
+    """Owner of one ``RayenProjPack*``: fp32 and fp64 images of a ``projection.Program`` on one device.  The fp64 tile
+    kernel's images are uploaded on request (``tile64_images``): until then the pack keeps the host arrays."""
     _layer = "proj"
 
     def __init__(self, arrays, device_index):
         a, ptr = arrays, _host_ptr
         self.n, self.m = int(a["n"]), int(a["m"])
+        self._arrays = {k: a[k] for k in ("G", "h", "Kinv", "w0", "soc_rows")}
         self._create(device_index, ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]), ptr(a["w0"]), self.n, self.m, int(a["m_lin"]),
                      ptr(a["soc_rows"]), int(a["soc_rows"].size), float(a["rho"]), float(a["sigma"]), float(a["alpha"]))
         if int(a.get("psd_dim", 0)):          # the set's LMI: the last rows of G are its PSD block, svec
@@ -1087,17 +1089,37 @@ class ProjPack(_SidePack):
                 _lib.check(_entry("rayen_proj_pack_set_psd")(self.handle, int(a["psd_row0"]), int(a["psd_dim"])),
                            "rayen_proj_pack_set_psd")
 
+    def tile64_images(self):
+        """Upload the fp64 tile kernel's images (once; an allocation and a copy: not while a stream is capturing).  A
+        program outside its envelope gets none."""
+        if self._arrays is not None:
+            a, ptr = self._arrays, _host_ptr
+            with torch.cuda.device(self.device_index):
+                _lib.check(_entry("rayen_proj_tile64_pack_set")(self.handle, ptr(a["G"]), ptr(a["h"]), ptr(a["Kinv"]),
+                                                                ptr(a["w0"]), ptr(a["soc_rows"]), int(a["soc_rows"].size)),
+                           "rayen_proj_tile64_pack_set")
+            self._arrays = None
 
-PROJ_KERNELS = ("wave", "tile")
+
+PROJ_KERNELS = ("wave", "tile")                 # the kernels that take fp32 input
+PROJ_KERNELS_F64 = ("wave", "tile64")           # ... and fp64 input ('tile64' is not in PROJ_KERNELS: it refuses fp32)
+_PROJ_KERNEL_NAMES = ("wave", "tile", "tile64")
 
 
-def _proj_entry(direction, kernel, dtype):
+def _proj_entry(direction, kernel, dtype, pack):
     """The library entry of ``kernel``: ``'wave'`` is rayen_proj.hip (wave per sample), ``'tile'`` rayen_proj_tile.hip (32
-    samples per workgroup on the matrix cores; fp32 only: an fp64 call is refused with ``E_UNSUPPORTED``)."""
-    if kernel not in PROJ_KERNELS:
-        raise ValueError(f"kernel must be one of {PROJ_KERNELS}, got {kernel!r}")
+    samples per workgroup on the matrix cores; fp32 only: an fp64 call is refused with ``E_UNSUPPORTED``), ``'tile64'``
+    rayen_proj_tile64.hip (16 samples per workgroup on the fp64 matrix cores; fp64 only: an fp32 call is refused with
+    ``E_UNSUPPORTED``)."""
+    if kernel not in _PROJ_KERNEL_NAMES:
+        raise ValueError(f"kernel must be one of {_PROJ_KERNEL_NAMES}, got {kernel!r}")
     if kernel == "wave":
         return _typed(f"rayen_proj_{direction}", dtype)
+    if kernel == "tile64":
+        if dtype != torch.float64:
+            raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_proj_tile64_{direction}")
+        pack.tile64_images()
+        return _entry(f"rayen_proj_tile64_{direction}_f64")
     if dtype != torch.float32:
         raise _lib.RayenError(_lib.E_UNSUPPORTED, f"rayen_proj_tile_{direction}")
     return _entry(f"rayen_proj_tile_{direction}_f32")
@@ -1105,16 +1127,16 @@ def _proj_entry(direction, kernel, dtype):
 
 def proj_forward_raw(q, pack, max_iters, eps, kernel='wave'):
     """``(z [B, n], iters [B] int32, vstar [B, m])`` through ``rayen_proj_forward_*`` (``kernel='tile'``:
-    ``rayen_proj_tile_forward_f32``)."""
+    ``rayen_proj_tile_forward_f32``; ``kernel='tile64'``: ``rayen_proj_tile64_forward_f64``)."""
     _check_rows(q, pack.n, pack, "q", "proj")
-    entry = _proj_entry("forward", kernel, q.dtype)
+    entry = _proj_entry("forward", kernel, q.dtype, pack)
     q = _dense_rows(q, pack.n)
     B = q.shape[0]
     z = torch.empty((B, pack.n), dtype=q.dtype, device=q.device)
     iters = torch.empty((B,), dtype=torch.int32, device=q.device)
     vstar = torch.empty((B, pack.m), dtype=q.dtype, device=q.device)
     with _on_device(q.device):
-        ws, nbytes = _workspace(pack, q, False, tile=kernel == "tile")
+        ws, nbytes = _workspace(pack, q, False, tile=kernel != "wave" and kernel)
         code = entry(
             pack.handle, _ptr(q), B, q.stride(0) if B else pack.n, _ptr(z), pack.n, _ptr(iters), _ptr(vstar),
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(q.device.index))
@@ -1124,15 +1146,16 @@ def proj_forward_raw(q, pack, max_iters, eps, kernel='wave'):
 
 def proj_backward_raw(grad_z, vstar, iters, pack, max_iters, eps, kernel='wave'):
     """``grad_q [B, n] = J grad_z`` row by row through ``rayen_proj_backward_*`` (``kernel='tile'``:
-    ``rayen_proj_tile_backward_f32``); ``vstar`` and ``iters`` may come from either kernel's forward."""
+    ``rayen_proj_tile_backward_f32``; ``kernel='tile64'``: ``rayen_proj_tile64_backward_f64``); ``vstar`` and ``iters`` may
+    come from any kernel's forward at the same precision."""
     _check_rows(grad_z, pack.n, pack, "grad_z", "proj")
-    entry = _proj_entry("backward", kernel, grad_z.dtype)
+    entry = _proj_entry("backward", kernel, grad_z.dtype, pack)
     g = _dense_rows(grad_z, pack.n)
     vstar, iters = vstar.contiguous(), iters.contiguous()
     B = g.shape[0]
     grad_q = torch.empty((B, pack.n), dtype=g.dtype, device=g.device)
     with _on_device(g.device):
-        ws, nbytes = _workspace(pack, g, True, tile=kernel == "tile")
+        ws, nbytes = _workspace(pack, g, True, tile=kernel != "wave" and kernel)
         code = entry(
             pack.handle, _ptr(g), B, g.stride(0) if B else pack.n, _ptr(vstar), _ptr(iters), _ptr(grad_q), pack.n,
             float(eps), int(max_iters), _ptr(ws), nbytes, _stream(g.device.index))
@@ -1241,6 +1264,53 @@ def _proj_tile_backward(ctx, grad_z, grad_iters, grad_vstar):
 
 
 euclid_project_tile.register_autograd(_proj_tile_backward, setup_context=_proj_setup_context)
+
+
+def proj_tile64_served(pack):
+    """Does the fp64 tile kernel serve this pack's program (its envelope: ``served()`` in rayen_proj_tile64_layout.h)?
+    Uploads the fp64 tile images on first use (an allocation and a copy: not while a stream is capturing)."""
+    pack.tile64_images()
+    return bool(_entry("rayen_proj_tile64_served")(pack.handle))
+
+
+@torch.library.custom_op("rayen_amd::euclid_project_tile64", mutates_args=())
+def euclid_project_tile64(q: torch.Tensor, pack_id: int, max_iters: int,
+                          eps: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``euclid_project`` in fp64 on the fp64 tile kernel (rayen_proj_tile64.hip)."""
+    return proj_forward_raw(q, _pack(pack_id), max_iters, eps, kernel="tile64")
+
+
+@euclid_project_tile64.register_fake
+def _(q, pack_id, max_iters, eps):
+    pack = _pack(pack_id)
+    B = q.shape[0]
+    return q.new_empty((B, pack.n)), q.new_empty((B,), dtype=torch.int32), q.new_empty((B, pack.m))
+
+
+@torch.library.custom_op("rayen_amd::euclid_project_tile64_bwd", mutates_args=())
+def euclid_project_tile64_bwd(grad_z: torch.Tensor, vstar: torch.Tensor, iters: torch.Tensor, pack_id: int, max_iters: int,
+                              eps: float) -> torch.Tensor:
+    return proj_backward_raw(grad_z, vstar, iters, _pack(pack_id), max_iters, eps, kernel="tile64")
+
+
+@euclid_project_tile64_bwd.register_fake
+def _(grad_z, vstar, iters, pack_id, max_iters, eps):
+    return grad_z.new_empty((grad_z.shape[0], _pack(pack_id).n))
+
+
+def _proj_tile64_backward(ctx, grad_z, grad_iters, grad_vstar):
+    vstar, iters = ctx.saved_tensors
+    if grad_z is None:
+        return None, None, None, None
+    pack = _pack(ctx.pack_id)
+    grad_q = torch.ops.rayen_amd.euclid_project_tile64_bwd(grad_z.to(vstar.dtype), vstar, iters, ctx.pack_id, ctx.max_iters,
+                                                           ctx.eps)
+    if ctx.width > pack.n:          # columns of q beyond n are not read
+        grad_q = torch.nn.functional.pad(grad_q, (0, ctx.width - pack.n))
+    return grad_q, None, None, None
+
+
+euclid_project_tile64.register_autograd(_proj_tile64_backward, setup_context=_proj_setup_context)
 
 
 # ------------------------------------------------------------------------------------------------

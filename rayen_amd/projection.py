@@ -367,7 +367,8 @@ class ProjectionModule(torch.nn.Module):
     ``Pi(q)`` otherwise (rayen/constraint_module.py:488-504).  Same mapper contract and buffer names as
     ``ConstraintModule``; ``project(q)`` returns ``(z, iters)``.  ``lmi=True`` serves a set with an LMI (the default
     raises ``NotImplementedError`` on one).  ``kernel``: ``'wave'`` (rayen_proj.hip, the default), ``'tile'``
-    (rayen_proj_tile.hip) or ``'auto'`` (the wave kernel where it serves the set, the tile kernel where only it does)."""
+    (rayen_proj_tile.hip on fp32 input, rayen_proj_tile64.hip on fp64 input) or ``'auto'`` (the wave kernel where it serves
+    the set at the input's precision, that precision's tile kernel where only it does)."""
 
     KERNELS = ('wave', 'tile', 'auto')
 
@@ -447,9 +448,13 @@ class ProjectionModule(torch.nn.Module):
         return _MirrorProject.apply(q2, self.constants(q2.dtype, q2.device), max_iters, eps)
 
     def _device_kernel(self, kernel, pack, dtype):
-        """``'wave'`` or ``'tile'`` for this call.  ``'auto'``: the wave kernel wherever it serves the set at this
-        precision (asked of the library with an empty batch: nothing is launched), else the tile kernel where it does,
-        else the wave kernel, whose refusal is the one reported.  No timing enters."""
+        """``'wave'``, ``'tile'`` or ``'tile64'`` for this call.  ``'tile'`` is the tile kernel of the input's precision
+        (``'tile64'`` on fp64).  ``'auto'``: the wave kernel wherever it serves the set at this precision (asked of the
+        library with an empty batch: nothing is launched), else that precision's tile kernel where it does, else the wave
+        kernel, whose refusal is the one reported.  No timing enters.  (The fp64 tile images are uploaded when first
+        asked for: make one call before capturing a graph.)"""
+        if kernel == 'tile':
+            return 'tile64' if dtype == torch.float64 else 'tile'
         if kernel != 'auto':
             return kernel
         from . import ops
@@ -457,8 +462,13 @@ class ProjectionModule(torch.nn.Module):
         cache = self.__dict__.setdefault("_auto_kernel", {})
         chosen = cache.get(key)                              # (fixed per pack and precision: asked once)
         if chosen is None:
-            tile = not ops.proj_wave_served(pack, dtype) and dtype == torch.float32 and ops.proj_tile_served(pack)
-            chosen = cache[key] = 'tile' if tile else 'wave'
+            chosen = 'wave'
+            if not ops.proj_wave_served(pack, dtype):
+                if dtype == torch.float32 and ops.proj_tile_served(pack):
+                    chosen = 'tile'
+                elif dtype == torch.float64 and ops.proj_tile64_served(pack):
+                    chosen = 'tile64'
+            cache[key] = chosen
         return chosen
 
     def project(self, q, max_iters=None, eps=None, kernel=None):
@@ -484,6 +494,8 @@ class ProjectionModule(torch.nn.Module):
                 z, iters, _ = ops.proj_forward_raw(q2, pack, max_iters, eps, kernel=chosen)
             elif chosen == 'tile':
                 z, iters, _ = torch.ops.rayen_amd.euclid_project_tile(q2, pack_id, max_iters, eps)
+            elif chosen == 'tile64':
+                z, iters, _ = torch.ops.rayen_amd.euclid_project_tile64(q2, pack_id, max_iters, eps)
             else:
                 z, iters, _ = torch.ops.rayen_amd.euclid_project(q2, pack_id, max_iters, eps)
             return z, iters
