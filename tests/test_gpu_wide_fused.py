@@ -17,6 +17,7 @@ from rayen_amd import _lib, ops, workloads                     # noqa: E402
 from rayen_amd.constraint_module import ConstraintModule       # noqa: E402
 from test_gpu_backward import _assert_gradient, _oracle_grad   # noqa: E402
 from test_gpu_parity import FP32_TOL, VIOLATION_TOL, _oracle_forward   # noqa: E402
+from wide_fused_bwd_cases import assert_active_names_a_maximiser   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -65,30 +66,6 @@ def test_against_the_oracle(name):
     assert np.array_equal(y[8], dp.consts.y0.astype(np.float32))          # the zero direction returns y0
 
 
-def _candidates64(consts, v):
-    """fp64 candidates of every segment: a list of ``[B, nrows]`` (linear rows) or ``[B, 1]`` arrays, by segment index."""
-    T = v @ consts.W.T
-    out = []
-    for s in consts.segments:
-        rows = T[:, s.row0:s.row0 + s.nrows]
-        if s.type == _lib.SEG_LIN:
-            out.append(rows)
-        elif s.type == _lib.SEG_QUAD_SYM:
-            out.append((T[:, s.aux_row] + np.sqrt(np.maximum(np.sum(rows * v[:, :s.nrows], axis=1), 0.0)))[:, None])
-        elif s.type == _lib.SEG_QUAD_FAC:
-            out.append((T[:, s.aux_row] + np.sqrt(np.sum(rows * rows, axis=1)))[:, None])
-        else:
-            assert s.type == _lib.SEG_SOC
-            cr, br = T[:, s.aux_row], T[:, s.aux_row + 1]
-            cp = np.sum(rows * rows, axis=1) - cr * cr
-            bp = 2 * br - 2 * cr * s.f0
-            disc = bp * bp - 4 * s.f1 * cp
-            root = np.sqrt(np.maximum(disc, 0.0))
-            cand = np.maximum((-bp - root) / (2 * s.f1), (-bp + root) / (2 * s.f1))
-            out.append(np.where(disc >= 0, cand, 0.0)[:, None])
-    return out
-
-
 @pytest.mark.parametrize("name", C.CASES)
 def test_kappa_and_active_against_fp64_on_the_same_pack(name):
     cs, layer, dp = _fused(name)
@@ -105,22 +82,7 @@ def test_kappa_and_active_against_fp64_on_the_same_pack(name):
     print(f"{name}: kappa error / max(1, kappa64): fused {np.max(err_f / scale):.3e}, products {np.max(err_p / scale):.3e}")
     assert np.all(err_f <= np.maximum(2 * err_p, 1e-5 * scale))
     # the constraint `active` names is a maximiser in fp64 (near-ties may pick another row than the products route)
-    af = af.cpu().numpy()
-    cands = _candidates64(dp.consts, v.double().cpu().numpy())
-    for b in range(v.shape[0]):
-        seg, row = int(af[b, 0]), int(af[b, 1])
-        if k64[b] <= 0:
-            assert seg == -1, (b, seg)
-            continue
-        assert 0 <= seg < len(cands), (b, seg)
-        s = dp.consts.segments[seg]
-        if s.type == _lib.SEG_LIN:
-            assert s.row0 <= row < s.row0 + s.nrows, (b, seg, row)
-            named = cands[seg][b, row - s.row0]
-        else:
-            assert row == 0
-            named = cands[seg][b, 0]
-        assert k64[b] - named <= 1e-5 * scale[b], (b, seg, row, k64[b], named)
+    assert_active_names_a_maximiser(dp.consts, v.double().cpu().numpy(), k64, af.cpu().numpy())
 
 
 @pytest.mark.parametrize("name", ["k129", "k190_n160"])

@@ -102,6 +102,28 @@ def candidates64(consts, v):
     return out
 
 
+def assert_active_names_a_maximiser(consts, v, k64, active):
+    """The rule of tests/test_gpu_wide_fused.py::test_kappa_and_active_against_fp64_on_the_same_pack: the constraint a
+    kernel's ``active [B, 2]`` names is a maximiser in fp64 within 1e-5 max(1, kappa64) (near-ties may pick another row).
+    ``v [B, n]`` fp64, ``k64 [B]`` the fp64 kappa of the same pack."""
+    cands = candidates64(consts, v)
+    scale = np.maximum(1.0, k64)
+    for b in range(v.shape[0]):
+        seg, row = int(active[b, 0]), int(active[b, 1])
+        if k64[b] <= 0:
+            assert seg == -1, (b, seg)
+            continue
+        assert 0 <= seg < len(cands), (b, seg)
+        s = consts.segments[seg]
+        if s.type == _lib.SEG_LIN:
+            assert s.row0 <= row < s.row0 + s.nrows, (b, seg, row)
+            named = cands[seg][b, row - s.row0]
+        else:
+            assert row == 0
+            named = cands[seg][b, 0]
+        assert k64[b] - named <= 1e-5 * scale[b], (b, seg, row, k64[b], named)
+
+
 def active64(consts, v):
     """(kappa [B], active segment [B] (-1: none)) in fp64."""
     cands = candidates64(consts, v)
@@ -165,3 +187,14 @@ def perm_offset(n_keys):
 
 def workspace(n_nonlinear, B):
     return 0 if n_nonlinear < 2 or B <= 0 else perm_offset(n_nonlinear + 1) + 4 * B
+
+
+def slots_bwd(plan, cus):
+    """Workgroups of the fused backward resident at once: as many a CU as LDS holds, at most three; ``cus`` =
+    ``wide_fused_cases.launch_cus(...)``.  The grid is ``wide_fused_cases.grid(B, slots)``."""
+    return cus * min(3, max(1, (160 * 1024) // plan["lds_bytes"]))
+
+
+def grouping_grid(B, cus):
+    """Workgroups of the count and scatter kernels: one per 256 rows, at most one per SIMD (they stride beyond)."""
+    return min(-(-B // 256), 4 * cus)

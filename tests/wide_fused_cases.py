@@ -101,3 +101,21 @@ def plan(n, k, n_rows, out_identity, segs):
              rows_pad=rows_w_pad + rows_e_pad, scratch_words=words, tile_bytes=tile_bytes, lds_bytes=lds,
              served=int(1 <= n <= MAX_N and k >= 1 and lds <= LDS))
     return p, seg_plans
+
+
+# ---------------------------------------------------------------- the launcher's grid, restated
+def launch_cus(cus, reserved=0):
+    """Compute units the persistent grids may fill (``launch_simds() / 4``): all but the reserved ones, at least one."""
+    return max(1, cus - reserved)
+
+
+def slots_fwd(plan, cus):
+    """Workgroups resident at once: as many a CU as LDS holds, at most four; ``cus`` = ``launch_cus(...)``."""
+    return cus * min(4, max(1, (160 * 1024) // plan["lds_bytes"]))
+
+
+def grid(B, slots):
+    """``persistent_grid(B, 32, slots, 1)`` of rayen_launch_geometry.h: the tiles dealt in equal rounds."""
+    n_tiles = -(-B // TILE)
+    rounds = -(-n_tiles // slots)
+    return -(-n_tiles // rounds)
