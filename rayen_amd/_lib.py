@@ -227,30 +227,16 @@ def load():
     for name in ("rayen_dc3_backward_f32", "rayen_dc3_backward_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
-    lib.rayen_dc3_tile_shape_served.restype = ctypes.c_int
-    lib.rayen_dc3_tile_shape_served.argtypes = [i32, i32, i32, i32]
-    lib.rayen_dc3_tile_pack_set.restype = ctypes.c_int
-    lib.rayen_dc3_tile_pack_set.argtypes = [p, p, p, p, p, p, p, p]
-    lib.rayen_dc3_tile_served.restype = ctypes.c_int
-    lib.rayen_dc3_tile_served.argtypes = [p]
-    lib.rayen_dc3_tile_workspace_bytes.restype = ctypes.c_int64
-    lib.rayen_dc3_tile_workspace_bytes.argtypes = [p, i64, i32, i32]
-    lib.rayen_dc3_tile_forward_f32.restype = ctypes.c_int
-    lib.rayen_dc3_tile_forward_f32.argtypes = [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]
-    lib.rayen_dc3_tile_backward_f32.restype = ctypes.c_int
-    lib.rayen_dc3_tile_backward_f32.argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
-    lib.rayen_dc3_tile64_shape_served.restype = ctypes.c_int
-    lib.rayen_dc3_tile64_shape_served.argtypes = [i32, i32, i32, i32]
-    lib.rayen_dc3_tile64_pack_set.restype = ctypes.c_int
-    lib.rayen_dc3_tile64_pack_set.argtypes = [p, p, p, p, p, p, p, p]
-    lib.rayen_dc3_tile64_served.restype = ctypes.c_int
-    lib.rayen_dc3_tile64_served.argtypes = [p]
-    lib.rayen_dc3_tile64_workspace_bytes.restype = ctypes.c_int64
-    lib.rayen_dc3_tile64_workspace_bytes.argtypes = [p, i64, i32, i32]
-    lib.rayen_dc3_tile64_forward_f64.restype = ctypes.c_int
-    lib.rayen_dc3_tile64_forward_f64.argtypes = [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]
-    lib.rayen_dc3_tile64_backward_f64.restype = ctypes.c_int
-    lib.rayen_dc3_tile64_backward_f64.argtypes = [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p]
+    for tile, dt in (("tile", "f32"), ("tile64", "f64")):           # the twin entry points of the two DC3 tile geometries
+        for name, restype, argtypes in (
+                ("shape_served", ctypes.c_int, [i32, i32, i32, i32]),
+                ("pack_set", ctypes.c_int, [p, p, p, p, p, p, p, p]),
+                ("served", ctypes.c_int, [p]),
+                ("workspace_bytes", ctypes.c_int64, [p, i64, i32, i32]),
+                ("forward_" + dt, ctypes.c_int, [p, p, i64, i64, p, i64, f64, f64, f64, i32, i32p, p, i64, i32p, p]),
+                ("backward_" + dt, ctypes.c_int, [p, p, i64, i64, p, i64, p, i64, f64, f64, i32, i32p, p, i64, p])):
+            fn = getattr(lib, f"rayen_dc3_{tile}_{name}")
+            fn.restype, fn.argtypes = restype, argtypes
     lib.rayen_proj_pack_create.restype = ctypes.c_int
     lib.rayen_proj_pack_create.argtypes = [p, p, p, p, i32, i32, i32, p, i32, f64, f64, f64, ctypes.POINTER(ctypes.c_void_p)]
     lib.rayen_proj_pack_set_psd.restype = ctypes.c_int

@@ -1,6 +1,7 @@
-// RayenDc3Pack: what rayen_dc3.hip (one lane per sample, image in LDS) and rayen_dc3_tile.hip (32 samples per workgroup
-// on the matrix cores) share.  The lane kernels' fields are filled by rayen_dc3_pack_create; the tile kernels' image is
-// uploaded by rayen_dc3_tile_pack_set on request (null: never asked for, or the shape is outside dc3_tile_served()).
+// RayenDc3Pack: what rayen_dc3.hip (one lane per sample, image in LDS) and rayen_dc3_tile_kernel.h (sample tiles on the
+// matrix cores, fp32 and fp64) share.  The lane kernels' fields are filled by rayen_dc3_pack_create; a tile geometry's image
+// is uploaded by rayen_dc3_tile_pack_set / rayen_dc3_tile64_pack_set on request (null: never asked for, or the shape is
+// outside the layout's served()).
 #pragma once
 
 #include <cstdint>
@@ -12,6 +13,6 @@ struct RayenDc3Pack {
   float* img32 = nullptr;
   double* img64 = nullptr;
   int32_t* perm = nullptr;      // [n] partial variables, then [no] other variables
-  float* tile_img = nullptr;    // rayen_dc3_tile_image.h (fp32 only)
-  double* tile_img64 = nullptr; // rayen_dc3_tile64_image.h (fp64 only; rayen_dc3_tile64_pack_set, likewise on request)
+  float* tile_img = nullptr;    // Dc3TileLayout32 of rayen_dc3_tile_image.h (fp32 only)
+  double* tile_img64 = nullptr; // Dc3TileLayout64 of the same header (fp64 only)
 };

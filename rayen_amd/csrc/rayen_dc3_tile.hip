@@ -1,634 +1,35 @@
-// method='DC3' on 32-sample tiles on the matrix cores: the iteration of rayen_dc3.hip (same mathematics, same batch-global
-// stop protocol, same contract; see that header) for sets whose image does not fit LDS.  Exact fp32 only
-// (v_mfma_f32_32x32x2_f32 is bit for bit an fmaf chain: the differences from the lane kernel are summation order).
-//
-//     r = relu(A1e p - b1e),  g_i = 0.5 p'Pe_i p + qe_i'p + re_i,  u_i = Pe_i p + qe_i
-//     grad = 2 A1e' r + sum_i 2 u_i relu(g_i),   s <- lr grad + momentum s,   p <- p - s
-//     y[partial] = p,  y[other] = c0 + C p
-//
-// Layout.  One workgroup of four waves owns a tile of 32 consecutive samples: a sample is a COLUMN of every product.
-// p, s and grad (n x 32, n <= 64: NX = 1 or 2 blocks of 32 rows) live in MFMA accumulator layout, 16 registers a block,
-// in EVERY wave (identical copies).  Lane l, register i of a block is column l & 31, row 8 (i >> 2) + 4 (l >> 5) + (i & 3);
-// the B operand of 32x32x2_f32 is B[k = l >> 5][j = l & 31]: so register i of p IS the B operand of one k-step of A1e p
-// (its half-waves hold rows r and r + 4), and a block of relu'd residuals is the B operand of A1e_b' r_b.  The host stores
-// the A images with k permuted to match and in per-lane order (rayen_dc3_tile_image.h): one coalesced 16-byte load a lane
-// feeds four MFMAs.  The images are STREAMED from global memory (L2-resident); none is held in LDS.
-//
-// Nothing whose size depends on m, nq or no is held: a block of r is consumed by A1e_b' r_b as soon as it is produced; a
-// u_i is folded into grad once its g_i is known (an in-lane sum over the lane's rows of p .* (u_i + qe_i), and one exchange
-// between the two half-waves that hold a column).  The work items -- the row blocks of A1e, then the quadratics -- go to
-// the waves round robin; the four partial grads meet in LDS (two workgroup barriers a step) and every wave then updates its
-// copy of (p, s) identically.  The order of every sum is fixed by the set alone: a column's arithmetic does not depend on
-// its tile-mates (MFMA columns do not mix, the half-wave exchange stays inside a column).
-//
-// Stop protocol: rayen_dc3.hip's, unchanged -- launches of kChunk steps, viol[t] by atomic max on the bits (columns beyond
-// B take no part), a launch leaves without writing if an earlier step met the rule, (p, s) ping-pong between two state
-// buffers (here in register order, [tile][2 NX][16][64]), one finishing launch that finds t*, replays t* - t0 steps where
-// needed and writes t*.  The backward recomputes p_0 .. p_{T-1} into the workspace ([T][tile][NX][16][64]) and sweeps back
-// with the J'x of rayen_dc3.hip's header; lr J' sbar is summed on its own and added to pbar once per step, as there.
-// Envelope: rayen::dc3_tile_served() (rayen_dc3_tile_image.h) -- fp32, 1 <= n <= 64, the image within 1 GiB.
-#include <hip/hip_runtime.h>
+// method='DC3' beyond LDS in fp32: the kernels of rayen_dc3_tile_kernel.h at the geometry Dc3Geom32 -- 32-sample tiles on
+// v_mfma_f32_32x32x2_f32, n in one or two blocks of 32 rows -- behind the six entry points of include/rayen_hip_dc3_tile.h.
+#include "rayen_dc3_tile_kernel.h"
 
-#include <cstdint>
-#include <new>
-#include <vector>
-
-#include "rayen_dc3_pack.h"
-#include "rayen_dc3_tile_image.h"
-
-namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kChunk = 32;                    // steps per launch (rayen_dc3.hip's)
-constexpr unsigned int kNanBits = 0x7fc00000u;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Img {
-  const float4 *A, *AT, *P, *PT, *C, *CT;
-  const float *b, *q, *r, *c0;
-  int n, no, Mb, nq, Cb, kg;
-};
-
-Img img_of(const RayenDc3Pack* p) {
-  const rayen::Dc3TileDims d = rayen::dc3_tile_dims(p->n, p->m, p->nq, p->no);
-  const float* base = p->tile_img;
-  auto f4 = [&](int64_t off) { return reinterpret_cast<const float4*>(base + off); };
-  Img im;
-  im.A = f4(d.off_A); im.AT = f4(d.off_AT); im.P = f4(d.off_P); im.PT = f4(d.off_PT); im.C = f4(d.off_C); im.CT = f4(d.off_CT);
-  im.b = base + d.off_b; im.q = base + d.off_q; im.r = base + d.off_r; im.c0 = base + d.off_c0;
-  im.n = d.n; im.no = d.no; im.Mb = d.Mb; im.nq = d.nq; im.Cb = d.Cb; im.kg = d.kg;
-  return im;
-}
-
-__device__ __forceinline__ int row_of(int i, int half) { return 8 * (i >> 2) + 4 * half + (i & 3); }
-
-// max that keeps a NaN once it has seen one (torch.max over a batch with a NaN is NaN)
-__device__ __forceinline__ float max_nan(float acc, float x) { return (x > acc || x != x) ? x : acc; }
-
-__device__ __forceinline__ void record_violation(unsigned int* slot, float v, bool live) {
-  if (!live) v = 0.0f;
-  for (int off = 32; off > 0; off >>= 1) v = max_nan(v, __shfl_xor(v, off, 64));
-  if ((threadIdx.x & 63) == 0) {
-    const unsigned int bits = v != v ? kNanBits : __float_as_uint(v);
-    if (bits != 0) atomicMax(slot, bits);
-  }
-}
-
-#define RAYEN_MFMA4(A, SRC, BASE, ACC)                                           \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x2f32((A).x, (SRC)[(BASE) + 0], ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x2f32((A).y, (SRC)[(BASE) + 1], ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x2f32((A).z, (SRC)[(BASE) + 2], ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_32x32x2f32((A).w, (SRC)[(BASE) + 3], ACC, 0, 0, 0)
-
-// a block of 32 values in accumulator layout from a plain array of whole blocks (b1e, qe_i, c0)
-__device__ __forceinline__ f32x16 load_block(const float* __restrict__ v, int half) {
-  const float4* v4 = reinterpret_cast<const float4*>(v);
-  f32x16 acc;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 x = v4[2 * g + half];
-    acc[4 * g + 0] = x.x; acc[4 * g + 1] = x.y; acc[4 * g + 2] = x.z; acc[4 * g + 3] = x.w;
-  }
-  return acc;
-}
-
-// acc += M_block src, M_block a rows-image block ([kg][64] float4 at `Mb`)
-template <int NX>
-__device__ __forceinline__ void times_rows(const float4* __restrict__ Mb, int kg, int lane, const f32x16 (&src)[NX],
-                                           f32x16& acc) {
-#pragma unroll
-  for (int g = 0; g < 4 * NX; ++g)
-    if (g < kg) {
-      const float4 A = Mb[g * 64 + lane];
-      RAYEN_MFMA4(A, src[g >> 2], 4 * (g & 3), acc);
-    }
-}
-
-// out += M_block' src, M_block a columns-image block ([NX][4][64] float4 at `Mb`), src one block of 32 rows
-template <int NX>
-__device__ __forceinline__ void times_columns(const float4* __restrict__ Mb, int lane, const f32x16& src, f32x16 (&out)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 A = Mb[(ob * 4 + g) * 64 + lane];
-      RAYEN_MFMA4(A, src, 4 * g, out[ob]);
-    }
-}
-
-template <int NX>
-__device__ __forceinline__ void zero(f32x16 (&x)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[ob][i] = 0.0f;
-}
-
-// the sum over a column of a value each lane holds for its rows: the two half-waves of a column exchange
-__device__ __forceinline__ float column_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-
-// the first quadratic of `wave`: the work items (row blocks, then quadratics) go round robin
-__device__ __forceinline__ int first_quadratic(const Img& im, int wave) { return (wave + kWaves - im.Mb % kWaves) % kWaves; }
-
-// u = Pe_c p + qe_c, qv = qe_c; returns g_c (the same in both lanes of a column)
-template <int NX>
-__device__ __forceinline__ float quadratic(const Img& im, int c, int lane, const f32x16 (&p)[NX], f32x16 (&u)[NX],
-                                           f32x16 (&qv)[NX]) {
-  const int half = lane >> 5;
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob) {
-    qv[ob] = load_block(im.q + ((size_t)c * NX + ob) * 32, half);
-    u[ob] = qv[ob];
-    times_rows<NX>(im.P + ((size_t)c * NX + ob) * im.kg * 64, im.kg, lane, p, u[ob]);
-  }
-  float g2 = 0.0f;
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) g2 = fmaf(p[ob][i], u[ob][i] + qv[ob][i], g2);
-  return fmaf(0.5f, column_sum(g2), im.r[c]);
-}
-
-// This wave's share of the residuals at p: returns max(0, its linear residuals, its g_i) (NaN kept); with GRAD also its
-// share of the correction direction, added to `part`.
-template <int NX, bool GRAD>
-__device__ __forceinline__ float eval_share(const Img& im, int wave, int lane, const f32x16 (&p)[NX], f32x16 (&part)[NX]) {
-  const int half = lane >> 5;
-  float viol = 0.0f;
-  for (int b = wave; b < im.Mb; b += kWaves) {
-    f32x16 acc = load_block(im.b + (size_t)b * 32, half);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = -acc[i];
-    times_rows<NX>(im.A + (size_t)b * im.kg * 64, im.kg, lane, p, acc);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float r = acc[i];
-      viol = max_nan(viol, r);
-      acc[i] = r > 0.0f ? r + r : (r != r ? r : 0.0f);
-    }
-    if constexpr (GRAD) times_columns<NX>(im.AT + (size_t)b * NX * 256, lane, acc, part);
-  }
-  for (int c = first_quadratic(im, wave); c < im.nq; c += kWaves) {
-    f32x16 u[NX], qv[NX];
-    const float g = quadratic<NX>(im, c, lane, p, u, qv);
-    viol = max_nan(viol, g);
-    if constexpr (GRAD) {
-      const float gg = g > 0.0f ? g + g : (g != g ? g : 0.0f);
-#pragma unroll
-      for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) part[ob][i] = fmaf(u[ob][i], gg, part[ob][i]);
-    }
-  }
-  return viol;
-}
-
-// part += this wave's share of lr J(p)' x   (J of the correction direction at p; rayen_dc3.hip's header)
-template <int NX>
-__device__ __forceinline__ void jacobian_transpose_share(const Img& im, int wave, int lane, const f32x16 (&p)[NX],
-                                                         const f32x16 (&x)[NX], float lr, f32x16 (&part)[NX]) {
-  const int half = lane >> 5;
-  const float lr2 = lr + lr;
-  for (int b = wave; b < im.Mb; b += kWaves) {
-    f32x16 r = load_block(im.b + (size_t)b * 32, half), dx;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      r[i] = -r[i];
-      dx[i] = 0.0f;
-    }
-    const float4* __restrict__ Ab = im.A + (size_t)b * im.kg * 64;
-#pragma unroll
-    for (int g = 0; g < 4 * NX; ++g)
-      if (g < im.kg) {
-        const float4 A = Ab[g * 64 + lane];
-        RAYEN_MFMA4(A, p[g >> 2], 4 * (g & 3), r);
-        RAYEN_MFMA4(A, x[g >> 2], 4 * (g & 3), dx);
-      }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dx[i] = r[i] > 0.0f ? lr2 * dx[i] : 0.0f;
-    times_columns<NX>(im.AT + (size_t)b * NX * 256, lane, dx, part);
-  }
-  for (int c = first_quadratic(im, wave); c < im.nq; c += kWaves) {
-    f32x16 u[NX], qv[NX];
-    const float g = quadratic<NX>(im, c, lane, p, u, qv);
-    float w = 0.0f;
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w = fmaf(u[ob][i], x[ob][i], w);
-    w = column_sum(w);
-    if (__any(g > 0.0f)) {
-      // 2 (relu(g) Pe' x + [g > 0] w (0.5 (Pe + Pe') p + qe)) = Pe' (2 relu(g) x + [g > 0] w p) + [g > 0] w (u + qe)
-      const float cg = g > 0.0f ? lr2 * g : 0.0f;
-      const float cw = g > 0.0f ? lr * w : 0.0f;
-      f32x16 z[NX];
-#pragma unroll
-      for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) z[ob][i] = fmaf(cg, x[ob][i], cw * p[ob][i]);
-#pragma unroll
-      for (int ob = 0; ob < NX; ++ob) {
-        times_rows<NX>(im.PT + ((size_t)c * NX + ob) * im.kg * 64, im.kg, lane, z, part[ob]);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) part[ob][i] = fmaf(cw, u[ob][i] + qv[ob][i], part[ob][i]);
-      }
-    }
-  }
-}
-
-// The four waves' partial sums meet in LDS; every wave leaves with the same total.  Two workgroup barriers.
-template <int NX>
-__device__ __forceinline__ void sum_partials(float* Pbuf, int wave, int lane, const f32x16 (&part)[NX], f32x16 (&total)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) Pbuf[((wave * NX + ob) * 16 + i) * 64 + lane] = part[ob][i];
-  __syncthreads();
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int at = (ob * 16 + i) * 64 + lane;
-      total[ob][i] = (Pbuf[at] + Pbuf[NX * 1024 + at]) + (Pbuf[2 * NX * 1024 + at] + Pbuf[3 * NX * 1024 + at]);
-    }
-  __syncthreads();
-}
-
-// one step from (p, s): every wave ends with the same new (p, s); returns this wave's share of the violation AT the old p
-template <int NX>
-__device__ __forceinline__ float step(const Img& im, float* Pbuf, int wave, int lane, float lr, float momentum,
-                                      f32x16 (&p)[NX], f32x16 (&s)[NX]) {
-  f32x16 part[NX], grad[NX];
-  zero<NX>(part);
-  const float v = eval_share<NX, true>(im, wave, lane, p, part);
-  sum_partials<NX>(Pbuf, wave, lane, part, grad);
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      s[ob][i] = lr * grad[ob][i] + momentum * s[ob][i];
-      p[ob][i] -= s[ob][i];
-    }
-  return v;
-}
-
-// rows of the caller's arrays <-> accumulator layout (columns beyond B: zero in, nothing out)
-template <int NX>
-__device__ __forceinline__ void load_rows(const float* __restrict__ row, bool live, int n, int half, f32x16 (&x)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int j = 32 * ob + row_of(i, half);
-      x[ob][i] = (live && j < n) ? row[j] : 0.0f;
-    }
-}
-
-template <int NX>
-__device__ __forceinline__ void load_state(const float* __restrict__ src, bool live, int lane, f32x16 (&x)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[ob][i] = live ? src[(ob * 16 + i) * 64 + lane] : 0.0f;
-}
-
-template <int NX>
-__device__ __forceinline__ void store_state(float* __restrict__ dst, bool live, int lane, const f32x16 (&x)[NX]) {
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (live) dst[(ob * 16 + i) * 64 + lane] = x[ob][i];
-}
-
-struct FwdArgs {
-  Img im;
-  const int32_t* perm;
-  const float* q;
-  int64_t B, ldq;
-  float* y;
-  int64_t ldy;
-  float lr, momentum, eps;
-  int max_steps;
-  int chunk;                 // >= 0: run chunk `chunk`; -1: the finishing launch
-  unsigned int* viol;        // [max_steps + 1]
-  float* state0;             // [tiles][2 NX][16][64] each: p then s (nullptr with a single chunk)
-  float* state1;
-  int32_t* tstar;
-  int32_t* nan_flag;
-};
-
-template <int NX>
-__global__ __launch_bounds__(kThreads) void dc3_tile_forward_kernel(const FwdArgs a) {
-  __shared__ float Pbuf[kWaves * NX * 1024];
-  __shared__ int sh_t;
-  const Img& im = a.im;
-  int chunk = a.chunk, nsteps;
-  const bool record = chunk >= 0;
-  if (record) {
-    const int t0 = chunk * kChunk;
-    if (threadIdx.x == 0) sh_t = 0;
-    __syncthreads();
-    for (int t = 1 + (int)threadIdx.x; t <= t0; t += kThreads)
-      if (__uint_as_float(a.viol[t]) < a.eps) atomicOr(&sh_t, 1);
-    __syncthreads();
-    if (sh_t) return;                             // an earlier step already met the stop rule: write nothing
-    nsteps = a.max_steps - t0 < kChunk ? a.max_steps - t0 : kChunk;
-  } else {
-    if (threadIdx.x == 0) sh_t = a.max_steps;
-    __syncthreads();
-    for (int t = 1 + (int)threadIdx.x; t < a.max_steps; t += kThreads)
-      if (__uint_as_float(a.viol[t]) < a.eps) atomicMin(&sh_t, t);
-    __syncthreads();
-    const int ts = sh_t;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.tstar = ts;
-    chunk = (ts - 1) / kChunk;
-    const int t0 = chunk * kChunk;
-    const int end = a.max_steps - t0 < kChunk ? a.max_steps : t0 + kChunk;
-    if (ts == end) return;                        // that chunk's own y is the answer
-    nsteps = ts - t0;
-  }
-  const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // (uniform, and the compiler knows it)
-  const int64_t tile = blockIdx.x;
-  const int64_t sample = tile * 32 + col;
-  const bool live = sample < a.B;
-  const int n = im.n;
-  f32x16 p[NX], s[NX];
-  if (chunk == 0) {
-    load_rows<NX>(a.q + sample * a.ldq, live, n, half, p);
-    zero<NX>(s);
-  } else {
-    const float* src = ((chunk & 1) ? a.state1 : a.state0) + (size_t)tile * 2 * NX * 1024;
-    load_state<NX>(src, live, lane, p);
-    load_state<NX>(src + NX * 1024, live, lane, s);
-  }
-  const int t0 = chunk * kChunk;
-  for (int st = 0; st < nsteps; ++st) {
-    const float v = step<NX>(im, Pbuf, wave, lane, a.lr, a.momentum, p, s);
-    if (record && st >= 1) record_violation(a.viol + t0 + st, v, live);
-  }
-  if (record) {
-    f32x16 none[NX];
-    const float v = eval_share<NX, false>(im, wave, lane, p, none);
-    record_violation(a.viol + t0 + nsteps, v, live);
-    if (wave == 0 && t0 + nsteps < a.max_steps) {
-      float* dst = ((chunk & 1) ? a.state0 : a.state1) + (size_t)tile * 2 * NX * 1024;
-      store_state<NX>(dst, live, lane, p);
-      store_state<NX>(dst + NX * 1024, live, lane, s);
-    }
-  }
-  // y[partial] = p (wave 0), y[other] = c0 + C p (the row blocks of C round robin)
-  float* __restrict__ yr = a.y + sample * a.ldy;
-  bool bad = false;
-  if (wave == 0) {
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int j = 32 * ob + row_of(i, half);
-        if (live && j < n) {
-          yr[a.perm[j]] = p[ob][i];
-          bad |= p[ob][i] != p[ob][i];
-        }
-      }
-  }
-  for (int cb = wave; cb < im.Cb; cb += kWaves) {
-    f32x16 acc = load_block(im.c0 + (size_t)cb * 32, half);
-    times_rows<NX>(im.C + (size_t)cb * im.kg * 64, im.kg, lane, p, acc);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int o = 32 * cb + row_of(i, half);
-      if (live && o < im.no) {
-        yr[a.perm[n + o]] = acc[i];
-        bad |= acc[i] != acc[i];
-      }
-    }
-  }
-  if (bad && a.nan_flag != nullptr) atomicOr(a.nan_flag, 1);
-}
-
-struct BwdArgs {
-  Img im;
-  const int32_t* perm;
-  const float* q;
-  int64_t B, ldq;
-  const float* grad_y;
-  int64_t ldg;
-  float* grad_q;
-  int64_t ldgq;
-  float lr, momentum;
-  int max_steps;
-  const int32_t* tstar;
-  float* traj;               // [max_steps][tiles][NX][16][64]
-};
-
-template <int NX>
-__global__ __launch_bounds__(kThreads) void dc3_tile_backward_kernel(const BwdArgs a) {
-  __shared__ float Pbuf[kWaves * NX * 1024];
-  const Img& im = a.im;
-  const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t tile = blockIdx.x;
-  const int64_t sample = tile * 32 + col;
-  const bool live = sample < a.B;
-  const int n = im.n;
-  int T_steps = *a.tstar;
-  if (T_steps > a.max_steps) T_steps = a.max_steps;
-  const size_t tiles = gridDim.x;
-  float* traj = a.traj + (size_t)tile * NX * 1024;             // step t: + t * tiles * NX * 1024
-  const size_t tstride = tiles * NX * 1024;
-  f32x16 p[NX], s[NX], w[NX];
-  load_rows<NX>(a.q + sample * a.ldq, live, n, half, p);
-  zero<NX>(s);
-  for (int t = 0; t < T_steps; ++t) {
-    if (wave == 0) store_state<NX>(traj + (size_t)t * tstride, live, lane, p);
-    if (t + 1 < T_steps) (void)step<NX>(im, Pbuf, wave, lane, a.lr, a.momentum, p, s);
-  }
-  __syncthreads();           // wave 0's trajectory is read by every wave below
-  // pbar_T = grad_y[partial] + C' grad_y[other]; s now holds sbar (zero beyond the last step)
-  const float* __restrict__ gy = a.grad_y + sample * a.ldg;
-#pragma unroll
-  for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int j = 32 * ob + row_of(i, half);
-      w[ob][i] = (live && j < n) ? gy[a.perm[j]] : 0.0f;
-    }
-  f32x16 part[NX], dj[NX];
-  if (im.Cb > 0) {
-    zero<NX>(part);
-    for (int cb = wave; cb < im.Cb; cb += kWaves) {
-      f32x16 go;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int o = 32 * cb + row_of(i, half);
-        go[i] = (live && o < im.no) ? gy[a.perm[n + o]] : 0.0f;
-      }
-      times_columns<NX>(im.CT + (size_t)cb * NX * 256, lane, go, part);
-    }
-    sum_partials<NX>(Pbuf, wave, lane, part, dj);
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[ob][i] += dj[ob][i];
-  }
-  zero<NX>(s);
-  for (int t = T_steps - 1; t >= 0; --t) {
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[ob][i] = a.momentum * s[ob][i] - w[ob][i];
-    load_state<NX>(traj + (size_t)t * tstride, live, lane, p);
-    zero<NX>(part);
-    jacobian_transpose_share<NX>(im, wave, lane, p, s, a.lr, part);
-    sum_partials<NX>(Pbuf, wave, lane, part, dj);
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[ob][i] += dj[ob][i];
-  }
-  if (wave == 0) {
-    float* __restrict__ gq = a.grad_q + sample * a.ldgq;
-#pragma unroll
-    for (int ob = 0; ob < NX; ++ob)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int j = 32 * ob + row_of(i, half);
-        if (live && j < n) gq[j] = w[ob][i];
-      }
-  }
-}
-
-int n_chunks(int max_steps) { return (max_steps + kChunk - 1) / kChunk; }
-
-// the scratch buffers: viol [max_steps + 1] | with more than one launch of steps, (p, s) in register order twice
-enum { kViol = 0, kState0 = 1, kState1 = 2 };
-rayen::WsLayout<3> forward_ws(const RayenDc3Pack* p, int64_t B, int max_steps) {
-  const size_t tiles = (size_t)((B + 31) / 32), nx = (size_t)(p->n + 31) / 32;
-  const size_t state = n_chunks(max_steps) > 1 ? tiles * 2 * nx * 1024 : 0;
-  return rayen::ws_layout<3>({{sizeof(unsigned int), (size_t)max_steps + 1}, {sizeof(float), state}, {sizeof(float), state}});
-}
-
-// the recomputed trajectory [max_steps][tiles][nx][16][64]
-rayen::WsLayout<1> backward_ws(const RayenDc3Pack* p, int64_t B, int max_steps) {
-  const size_t tiles = (size_t)((B + 31) / 32), nx = (size_t)(p->n + 31) / 32;
-  return rayen::ws_layout<1>({{sizeof(float), (size_t)max_steps * tiles * nx * 1024}});
-}
-
-bool served(const RayenDc3Pack* p) {
-  return p != nullptr && p->tile_img != nullptr && p->perm != nullptr && rayen::dc3_tile_served(p->n, p->m, p->nq, p->no);
-}
-
-template <int NX>
-int launch_forward(FwdArgs a, hipStream_t stream) {
-  const unsigned grid = (unsigned)((a.B + 31) / 32);
-  const int chunks = n_chunks(a.max_steps);
-  for (int c = 0; c <= chunks; ++c) {
-    a.chunk = c < chunks ? c : -1;
-    hipLaunchKernelGGL(dc3_tile_forward_kernel<NX>, dim3(grid), dim3(kThreads), 0, stream, a);
-    if (hipGetLastError() != hipSuccess) return RAYEN_E_LAUNCH;
-  }
-  return RAYEN_OK;
-}
-
-template <int NX>
-int launch_backward(const BwdArgs& a, hipStream_t stream) {
-  const unsigned grid = (unsigned)((a.B + 31) / 32);
-  hipLaunchKernelGGL(dc3_tile_backward_kernel<NX>, dim3(grid), dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
-}
-
-}  // namespace
+namespace tile = rayen::dc3_tile;
+using G = tile::Dc3Geom32;
 
 extern "C" {
 
-int rayen_dc3_tile_shape_served(int32_t n, int32_t m, int32_t nq, int32_t no) {
-  return rayen::dc3_tile_served(n, m, nq, no) ? 1 : 0;
-}
+int rayen_dc3_tile_shape_served(int32_t n, int32_t m, int32_t nq, int32_t no) { return tile::shape_served<G>(n, m, nq, no); }
 
 int rayen_dc3_tile_pack_set(RayenDc3Pack* p, const double* A1e, const double* b1e, const double* Pe, const double* qe,
                             const double* re, const double* C, const double* c0) {
-  if (p == nullptr || (p->m > 0 && (A1e == nullptr || b1e == nullptr)) ||
-      (p->nq > 0 && (Pe == nullptr || qe == nullptr || re == nullptr)) || (p->no > 0 && (C == nullptr || c0 == nullptr)))
-    return RAYEN_E_BAD_ARG;
-  if (p->tile_img != nullptr) return RAYEN_OK;
-  std::vector<float> h;
-  // a shape outside the envelope gets no image: the calls answer RAYEN_E_UNSUPPORTED
-  if (!rayen::dc3_tile_image(p->n, p->m, p->nq, p->no, A1e, b1e, Pe, qe, re, C, c0, &h)) return RAYEN_OK;
-  const int rc = rayen::check_device(p->device);
-  if (rc != RAYEN_OK) return rc;
-  if (!rayen::upload_image(h, &p->tile_img)) {
-    if (p->tile_img) (void)hipFree(p->tile_img);
-    p->tile_img = nullptr;
-    return RAYEN_E_ALLOC;
-  }
-  return RAYEN_OK;
+  return tile::pack_set<G>(p, A1e, b1e, Pe, qe, re, C, c0);
 }
 
-int rayen_dc3_tile_served(const RayenDc3Pack* pack) { return served(pack) ? 1 : 0; }
+int rayen_dc3_tile_served(const RayenDc3Pack* pack) { return tile::served<G>(pack) ? 1 : 0; }
 
 int64_t rayen_dc3_tile_workspace_bytes(const RayenDc3Pack* p, int64_t B, int32_t max_steps, int32_t backward) {
-  if (p == nullptr || B < 0 || max_steps < 1) return -1;
-  return (int64_t)(backward ? backward_ws(p, B, max_steps).total : forward_ws(p, B, max_steps).total);
+  return tile::workspace_bytes<G>(p, B, max_steps, backward);
 }
 
 int rayen_dc3_tile_forward_f32(const RayenDc3Pack* p, const float* q, int64_t B, int64_t ldq, float* y, int64_t ldy,
                                double lr, double momentum, double eps, int32_t max_steps, int32_t* tstar, void* ws,
                                int64_t ws_bytes, int32_t* nan_flag, void* stream) {
-  if (p == nullptr || B < 0 || max_steps < 1 || tstar == nullptr) return RAYEN_E_BAD_ARG;
-  if (B > 0 && (q == nullptr || y == nullptr || ldq < p->n || ldy < p->k)) return RAYEN_E_BAD_ARG;
-  if (B > ((int64_t)1 << 31) - kThreads) return RAYEN_E_BAD_ARG;
-  if (!served(p)) return RAYEN_E_UNSUPPORTED;
-  const rayen::WsLayout<3> w = forward_ws(p, B, max_steps);
-  if (ws == nullptr || ws_bytes < (int64_t)w.total) return RAYEN_E_BAD_ARG;
-  const int rc = rayen::check_device(p->device);
-  if (rc != RAYEN_OK) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(ws, 0, w.bytes[kViol], s) != hipSuccess) return RAYEN_E_LAUNCH;
-  if (B == 0) {
-    // an empty batch takes no step (the reference's maximum over nothing raises)
-    return hipMemsetAsync(tstar, 0, sizeof(int32_t), s) == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
-  }
-  FwdArgs a;
-  a.im = img_of(p);
-  a.perm = p->perm;
-  a.q = q; a.B = B; a.ldq = ldq; a.y = y; a.ldy = ldy;
-  a.lr = (float)lr; a.momentum = (float)momentum; a.eps = (float)eps;
-  a.max_steps = max_steps;
-  a.chunk = 0;
-  a.viol = w.at<unsigned int>(ws, kViol);
-  a.state0 = w.at<float>(ws, kState0);      // (null with a single chunk)
-  a.state1 = w.at<float>(ws, kState1);
-  a.tstar = tstar;
-  a.nan_flag = nan_flag;
-  return p->n <= 32 ? launch_forward<1>(a, s) : launch_forward<2>(a, s);
+  return tile::forward<G>(p, q, B, ldq, y, ldy, lr, momentum, eps, max_steps, tstar, ws, ws_bytes, nan_flag, stream);
 }
 
 int rayen_dc3_tile_backward_f32(const RayenDc3Pack* p, const float* q, int64_t B, int64_t ldq, const float* grad_y,
                                 int64_t ldg, float* grad_q, int64_t ldgq, double lr, double momentum, int32_t max_steps,
                                 const int32_t* tstar, void* ws, int64_t ws_bytes, void* stream) {
-  if (p == nullptr || B < 0 || max_steps < 1 || tstar == nullptr) return RAYEN_E_BAD_ARG;
-  if (B > 0 && (q == nullptr || grad_y == nullptr || grad_q == nullptr || ldq < p->n || ldg < p->k || ldgq < p->n))
-    return RAYEN_E_BAD_ARG;
-  if (B > ((int64_t)1 << 31) - kThreads) return RAYEN_E_BAD_ARG;
-  if (!served(p)) return RAYEN_E_UNSUPPORTED;
-  const rayen::WsLayout<1> w = backward_ws(p, B, max_steps);
-  if (B > 0 && (ws == nullptr || ws_bytes < (int64_t)w.total)) return RAYEN_E_BAD_ARG;
-  const int rc = rayen::check_device(p->device);
-  if (rc != RAYEN_OK || B == 0) return rc;
-  BwdArgs a;
-  a.im = img_of(p);
-  a.perm = p->perm;
-  a.q = q; a.B = B; a.ldq = ldq; a.grad_y = grad_y; a.ldg = ldg; a.grad_q = grad_q; a.ldgq = ldgq;
-  a.lr = (float)lr; a.momentum = (float)momentum;
-  a.max_steps = max_steps;
-  a.tstar = tstar;
-  a.traj = w.at<float>(ws, 0);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return p->n <= 32 ? launch_backward<1>(a, s) : launch_backward<2>(a, s);
+  return tile::backward<G>(p, q, B, ldq, grad_y, ldg, grad_q, ldgq, lr, momentum, max_steps, tstar, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -941,14 +941,14 @@ def dc3_lane_served(pack, dtype):
 
 
 def dc3_tile_served(pack):
-    """Does the tile kernel serve this pack (its envelope: ``dc3_tile_served()`` in rayen_dc3_tile_image.h)?  Uploads the
+    """Does the tile kernel serve this pack (its envelope: ``Dc3TileLayout32::served()`` in rayen_dc3_tile_image.h)?  Uploads the
     tile image on first use (an allocation and a copy: not while a stream is capturing)."""
     pack.tile_images()
     return bool(_entry("rayen_dc3_tile_served")(pack.handle))
 
 
 def dc3_tile64_served(pack):
-    """Does the fp64 tile kernel serve this pack (its envelope: ``dc3_tile64_served()`` in rayen_dc3_tile64_image.h)?
+    """Does the fp64 tile kernel serve this pack (its envelope: ``Dc3TileLayout64::served()`` in rayen_dc3_tile_image.h)?
     Uploads the fp64 tile image on first use (an allocation and a copy: not while a stream is capturing)."""
     pack.tile64_images()
     return bool(_entry("rayen_dc3_tile64_served")(pack.handle))

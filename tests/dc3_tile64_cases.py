@@ -123,11 +123,11 @@ def reorder_gap(call):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the image layout, restated (rayen_dc3_tile64_image.h)
+# the image layout, restated (Dc3TileLayout64 of rayen_dc3_tile_image.h; its kp is the kp here, kg is not kept there)
 # ------------------------------------------------------------------------------------------------------------------
 
 def dims(n, m, nq, no):
-    """The offsets (in doubles) and counts of ``rayen::dc3_tile64_dims``."""
+    """The offsets (in doubles) and counts of ``rayen::Dc3TileLayout64::dims``."""
     nx, kg = (n + 15) // 16, (n + 3) // 4
     kp, Mb, Cb = (kg + 1) // 2, (m + 15) // 16, (no + 15) // 16
     sizes = [("A", Mb * kp * 128), ("AT", Mb * nx * 256), ("b", Mb * 16), ("P", nq * nx * kp * 128),

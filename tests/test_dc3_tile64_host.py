@@ -71,7 +71,8 @@ PROBE = r"""
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "rayen_dc3_tile64_image.h"
+#include "rayen_dc3_tile_image.h"
+using Layout = rayen::Dc3TileLayout64;
 static std::vector<double> take(FILE* f, size_t count) {
   std::vector<double> v(count + 1);
   if (count && fread(v.data(), sizeof(double), count, f) != count) exit(3);
@@ -86,9 +87,9 @@ int main(int argc, char** argv) {
                       r = take(f, nq), C = take(f, (size_t)no * n), c0 = take(f, no);
   fclose(f);
   std::vector<double> h;
-  if (!rayen::dc3_tile64_image(n, m, nq, no, A.data(), b.data(), P.data(), q.data(), r.data(), C.data(), c0.data(), &h)) return 4;
-  if ((int64_t)h.size() != rayen::dc3_tile64_dims(n, m, nq, no).total) return 5;
-  if (rayen::dc3_tile64_image(65, m, nq, no, A.data(), b.data(), P.data(), q.data(), r.data(), C.data(), c0.data(), &h)) return 6;
+  if (!Layout::image(n, m, nq, no, A.data(), b.data(), P.data(), q.data(), r.data(), C.data(), c0.data(), &h)) return 4;
+  if ((int64_t)h.size() != Layout::dims(n, m, nq, no).total) return 5;
+  if (Layout::image(65, m, nq, no, A.data(), b.data(), P.data(), q.data(), r.data(), C.data(), c0.data(), &h)) return 6;
   FILE* o = fopen(argv[6], "wb");
   if (!o || fwrite(h.data(), sizeof(double), h.size(), o) != h.size()) return 7;
   fclose(o);
