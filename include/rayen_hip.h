@@ -159,7 +159,8 @@ enum {
   RAYEN_KERNEL_PRODUCTS = 9,  /* wide sets (ABI v7): the epilogue over products T = v W_ext' of a library GEMM */
   RAYEN_KERNEL_PAIR_WL = 11,  /* f16 pairs, the image of W resident in LDS, four waves per SIMD on groups of 32 samples (round 6) */
   RAYEN_KERNEL_LMI_BLOCK = 10, /* one workgroup per sample, the packed lower triangle in LDS (one LMI to ~280 x 280 + linear rows; round 5) */
-  RAYEN_KERNEL_WIDE_FUSED = 12 /* wide sets without the products matrix (rayen_hip_wide_fused.h): rayen_ray_project_wide_fused_f32 */
+  RAYEN_KERNEL_WIDE_FUSED = 12, /* wide sets without the products matrix (rayen_hip_wide_fused.h): rayen_ray_project_wide_fused_f32 */
+  RAYEN_KERNEL_WIDE_FUSED64 = 13 /* the same in fp64 (rayen_hip_wide_fused64.h): rayen_ray_project_wide_fused64_f64 */
 };
 int rayen_last_forward_kernel(void);
 
@@ -550,6 +551,8 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 /* ---- Wide sets (n > 128) in one launch, without the products matrix of the ABI v7 route (additive to ABI v15) */
 #include "rayen_hip_wide_fused.h"
 #include "rayen_hip_wide_fused_bwd.h"
+/* ---- ... and the forward in fp64 (n > 64) on the fp64 matrix cores (additive to ABI v15) */
+#include "rayen_hip_wide_fused64.h"
 
 #ifdef __cplusplus
 }

@@ -100,7 +100,8 @@ class ConstraintModule(torch.nn.Module):
             raise ValueError(f"wide_kernel={wide_kernel!r} chooses a kernel of method 'RAYEN'; this module's method is {method!r}")
         # method='RAYEN' on wide sets (n beyond the register-resident kernels, ops._WIDE_MIN_N): 'products' (the default: a
         # library GEMM and rayen_wide.hip over its products) or 'fused' (rayen_wide_fused.hip: one launch, no products
-        # matrix; fp32, no LMI, n <= 1024 -- anything else takes the module's loud path).  No effect on narrower sets.  The
+        # matrix; fp32, no LMI, n <= 1024 -- anything else takes the module's loud path) or 'fused64' (its fp64 twin,
+        # rayen_wide_fused64.hip: fp64 input, no LMI, n <= 1024 -- anything else likewise).  No effect on narrower sets.  The
         # backward is chosen by `wide_backward` below (the products route by default).  There is no 'auto': both serve the same sets, and no timing
         # enters a dispatch here.
         self.wide_kernel = wide_kernel
@@ -338,16 +339,17 @@ class ConstraintModule(torch.nn.Module):
         try:
             dp, pack_id = self.device_pack(v.device)
             need_active = torch.is_grad_enabled() and v.requires_grad
-            fused = not old_head and getattr(self, "wide_kernel", 'products') == 'fused'
+            wide = 'products' if old_head else getattr(self, "wide_kernel", 'products')
+            fused = wide == 'fused'
             if not need_active and type(v) is torch.Tensor and not torch.compiler.is_compiling():
                 # plain inference call: straight to the C ABI (the same code the registered op runs; the dispatcher
                 # layers around a custom op cost ~10 us per call, as much as the kernel at small batches)
-                y, _, _ = ops.project_raw(v, dp, want_active=False, old_head=old_head, want_kappa=False,
-                                          wide_kernel='fused' if fused else 'products')
+                y, _, _ = ops.project_raw(v, dp, want_active=False, old_head=old_head, want_kappa=False, wide_kernel=wide)
                 return y, None
-            if not old_head and getattr(self, "wide_backward", 'products') != 'products':
-                y, kappa, _ = torch.ops.rayen_amd.ray_project_wide(v, pack_id, need_active, 'fused' if fused else 'products',
-                                                                   self.wide_backward)
+            if not old_head and (getattr(self, "wide_backward", 'products') != 'products' or wide == 'fused64'):
+                # (the op that carries both strings: 'fused64' has no op of its own)
+                y, kappa, _ = torch.ops.rayen_amd.ray_project_wide(v, pack_id, need_active, wide,
+                                                                   getattr(self, "wide_backward", 'products'))
             elif fused:
                 y, kappa, _ = torch.ops.rayen_amd.ray_project_wide_fused(v, pack_id, need_active)
             else:
@@ -592,7 +594,7 @@ class ConstraintModule(torch.nn.Module):
                     and not self._refused(x) and x.dtype in (torch.float32, torch.float64)
                     and self.n < ops._WIDE_MIN_N[x.dtype]      # (wide sets: GEMM + products epilogue, ops.project_raw)
                     # (a set with an LMI may take the wide route earlier: wide_kernel='fused' gets its refusal there)
-                    and not (getattr(self, "wide_kernel", 'products') == 'fused' and self.cs.has_lmi_constraints)):
+                    and not (getattr(self, "wide_kernel", 'products') in ('fused', 'fused64') and self.cs.has_lmi_constraints)):
                 try:
                     dp, _ = self.device_pack(x.device)
                     fn = ops._entry(ops._FWD[(x.dtype, False)])

@@ -1,6 +1,7 @@
 // C-ABI entry points of librayen_hip.so (declared in include/rayen_hip.h).
 #include "rayen_internal.h"
 #include "rayen_pair_image.h"
+#include "rayen_wide_fused64_layout.h"
 
 #include <atomic>
 #include <cmath>
@@ -820,6 +821,7 @@ void rayen_pack_destroy(RayenPack* p) {
   if (p->wide) wide_free(p->wide);
   if (p->wf32) wide_fused_free(p->wf32);
   if (p->wfb32) wide_fused_bwd_free(p->wfb32);
+  if (p->wf64) wide_fused64_free(p->wf64);
   if (p->q32) lmi_quad_free(p->q32);
   if (p->w32) lmi_wave_free(p->w32);
   if (p->w64) lmi_wave_free(p->w64);
@@ -919,6 +921,28 @@ int rayen_ray_project_wide_fused_f32(const RayenPack* p, const float* v, int64_t
   if (rc) return rc;
   g_last_forward = RAYEN_KERNEL_WIDE_FUSED;
   return wide_fused_forward(p, v, B, ldv, y, ldy, kappa, active, nan_flag, static_cast<hipStream_t>(stream));
+}
+
+int rayen_wide_fused64_served(const RayenPack* p) { return (p != nullptr && wide_fused64_served(p)) ? 1 : 0; }
+
+int rayen_wide_fused64_plan(const RayenPack* p, int32_t samples, int64_t* out) {
+  if (p == nullptr || out == nullptr || (samples != 0 && samples != 16 && samples != 32)) return RAYEN_E_BAD_ARG;
+  WideFused64Plan pl;
+  if (!wide_fused64_plan_of(p, samples, &pl)) return RAYEN_E_UNSUPPORTED;
+  const int64_t vals[13] = {pl.n, pl.kp, pl.ks, pl.samples, pl.rows_w_pad, pl.nb_w, pl.rows_e_pad, pl.nb_e, pl.rows_pad,
+                            pl.scratch_words, pl.tile_bytes, pl.lds_bytes, pl.served};
+  for (int i = 0; i < 13; ++i) out[i] = vals[i];
+  return RAYEN_OK;
+}
+
+int rayen_ray_project_wide_fused64_f64(const RayenPack* p, const double* v, int64_t B, int64_t ldv, double* y, int64_t ldy,
+                                       double* kappa, int32_t* active, int32_t* nan_flag, int32_t samples, void* stream) {
+  if (p == nullptr || B < 0 || (B > 0 && v == nullptr) || ldv < p->n || (y != nullptr && ldy < p->k)) return RAYEN_E_BAD_ARG;
+  if (B > ((int64_t)1 << 31) - 32 || (samples != 0 && samples != 16 && samples != 32)) return RAYEN_E_BAD_ARG;
+  const int rc = check_ready<double>(p, false);
+  if (rc) return rc;
+  g_last_forward = RAYEN_KERNEL_WIDE_FUSED64;
+  return wide_fused64_forward(p, v, B, ldv, y, ldy, kappa, active, nan_flag, samples, static_cast<hipStream_t>(stream));
 }
 
 int rayen_wide_fused_bwd_served(const RayenPack* p, int32_t f64) {

@@ -65,11 +65,13 @@ struct Ws8Image;        // rayen_mfma_pair_ws8.hip
 struct WideImage;       // rayen_wide.hip
 struct WideFusedImage;  // rayen_wide_fused_common.h
 struct WideFusedBwdImage;  // rayen_wide_fused_bwd.hip
+struct WideFused64Image;   // rayen_wide_fused64.hip
+struct WideFused64Plan;    // rayen_wide_fused64_layout.h
 
 }  // namespace rayen
 
 // Immutable after rayen_pack_create returns (every device image is built there), so it is shared by threads and
-// streams without a lock -- but for `wf32` and `wfb32`, the images of the opt-in fused wide forward and backward, which their
+// streams without a lock -- but for `wf32`, `wfb32` and `wf64`, the images of the opt-in fused wide forwards and backward, which their
 // first calls build under a lock of their own (rayen_wide_fused_common.h).
 struct RayenPack {
   int device = -1;
@@ -114,6 +116,9 @@ struct RayenPack {
   // the fused wide backward's images, lazy in the same way and under the same lock (it shares wf32's W where that exists)
   mutable rayen::WideFusedBwdImage* wfb32 = nullptr;
   mutable int wfb32_state = 0;
+  // the fp64 fused wide forward's image (rayen_wide_fused64.hip), lazy in the same way and under the same lock
+  mutable rayen::WideFused64Image* wf64 = nullptr;
+  mutable int wf64_state = 0;
   double check_split = -1.0, check_exact = -1.0, check_pair = -1.0;  // worst row errors against fp64 (fp32_selfcheck)
   // [linear rows, quadratics, cones] + ONE LMI the lane kernels do not hold: the lane kernel evaluates everything but the
   // LMI (generic image built with skip_lmi), the workgroup-per-sample kernel the LMI on top of that (rayen_abi.hip)
@@ -140,6 +145,14 @@ bool wide_fused_served(const RayenPack* p);
 void wide_fused_free(WideFusedImage* img);
 int wide_fused_forward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy, float* kappa,
                        int32_t* active, int32_t* nan_flag, hipStream_t stream);
+
+// the same in fp64 (rayen_wide_fused64.hip): no LMI, n <= 1024, a tile of 32 or 16 samples (`samples`; 0: the plan's choice)
+// and the scratch within LDS.  wide_fused64_plan_of: the plan for `samples` (false: the pack has no plan -- null, or an LMI)
+bool wide_fused64_served(const RayenPack* p);
+bool wide_fused64_plan_of(const RayenPack* p, int samples, WideFused64Plan* plan);
+void wide_fused64_free(WideFused64Image* img);
+int wide_fused64_forward(const RayenPack* p, const double* v, int64_t B, int64_t ldv, double* y, int64_t ldy, double* kappa,
+                         int32_t* active, int32_t* nan_flag, int samples, hipStream_t stream);
 
 // their backward without T and C (rayen_wide_fused_bwd.hip): fp32, no LMI, n <= 1024, its tiles within LDS
 bool wide_fused_bwd_served(const RayenPack* p);

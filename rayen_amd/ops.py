@@ -162,11 +162,11 @@ def _wide_route(v, pack, force_generic, old_head):
     return Wt
 
 
-WIDE_KERNELS = ('products', 'fused')
+WIDE_KERNELS = ('products', 'fused', 'fused64')
 
 
 def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old_head=False, out=None,
-                want_kappa=True, wide_kernel='products'):
+                want_kappa=True, wide_kernel='products', wide_samples=0):
     """Direct call of the C ABI on an existing ``DevicePack``; returns (y|None, kappa|None, active|None).
 
     ``old_head``: the ``RAYEN_old`` step rule; ``v`` then carries ``beta`` in column ``n``.
@@ -174,8 +174,11 @@ def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old
     rank's rows of a gather buffer -- instead of a fresh allocation.
     ``wide_kernel``: what serves a call that takes the wide route (``_wide_route``): ``'products'`` -- the library GEMM and
     the epilogue over its products -- or ``'fused'`` -- ``rayen_ray_project_wide_fused_f32`` (rayen_wide_fused.hip): one
-    launch, no GEMM and no products matrix; fp32, no LMI, n <= 1024, anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on
-    a call that does not take the wide route."""
+    launch, no GEMM and no products matrix; fp32, no LMI, n <= 1024, anything else is ``RAYEN_E_UNSUPPORTED`` -- or
+    ``'fused64'`` -- its fp64 twin ``rayen_ray_project_wide_fused64_f64`` (rayen_wide_fused64.hip): fp64, no LMI, n <= 1024,
+    anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on a call that does not take the wide route.
+    ``wide_samples`` (tests and measurements): the sample tile of ``'fused64'``, 16 or 32; 0 leaves it to the plan.  The bits
+    of a row do not depend on it."""
     if wide_kernel not in WIDE_KERNELS:
         raise ValueError(f"wide_kernel must be one of {WIDE_KERNELS}, got {wide_kernel!r}")
     _check_input(v, pack)
@@ -195,6 +198,15 @@ def project_raw(v, pack, want_y=True, force_generic=False, want_active=True, old
     active = torch.empty((B, 2), dtype=torch.int32, device=v.device) if want_active else None
     Wt = _wide_route(v, pack, force_generic, old_head) if B else None
     with _on_device(v.device):
+        if Wt is not None and wide_kernel == 'fused64':
+            if v.dtype != torch.float64:
+                code = _lib.E_UNSUPPORTED        # (the kernel is fp64 only; fp32 has 'fused')
+            else:
+                code = _entry("rayen_ray_project_wide_fused64_f64")(
+                    pack.handle, _ptr(v), B, v.stride(0), _ptr(y), y.stride(0) if y is not None else k, _ptr(kappa),
+                    _ptr(active), _ptr(pack.nan_flag), int(wide_samples), _stream(v.device.index))
+            _lib.check(code, "rayen_ray_project_wide_fused64")
+            return y, kappa, active
         if Wt is not None and wide_kernel == 'fused':
             if v.dtype != torch.float32:
                 code = _lib.E_UNSUPPORTED        # (the fused kernel is fp32 only: rayen_wide_fused_served(pack, 1) == 0)
