@@ -553,6 +553,8 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 #include "rayen_hip_wide_fused_bwd.h"
 /* ---- ... and the forward in fp64 (n > 64) on the fp64 matrix cores (additive to ABI v15) */
 #include "rayen_hip_wide_fused64.h"
+/* ---- ... and its backward in fp64 (additive to ABI v15) */
+#include "rayen_hip_wide_fused_bwd64.h"
 
 #ifdef __cplusplus
 }

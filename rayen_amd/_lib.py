@@ -73,6 +73,10 @@ EXPORTS_WIDE_FUSED_BWD = ("rayen_wide_fused_bwd_served", "rayen_wide_fused_bwd_w
 # additive to ABI v15, declared in include/rayen_hip_wide_fused64.h (which rayen_hip.h includes, like the six above);
 # tests/test_wide_fused64_host.py holds the two against each other
 EXPORTS_WIDE_FUSED64 = ("rayen_wide_fused64_served", "rayen_wide_fused64_plan", "rayen_ray_project_wide_fused64_f64")
+# additive to ABI v15, declared in include/rayen_hip_wide_fused_bwd64.h (which rayen_hip.h includes, like the seven above);
+# tests/test_wide_fused_bwd64_host.py holds the two against each other
+EXPORTS_WIDE_FUSED_BWD64 = ("rayen_wide_fused_bwd64_served", "rayen_wide_fused_bwd64_plan",
+                            "rayen_wide_fused_bwd64_workspace_bytes", "rayen_ray_project_wide_fused_bwd_f64")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 KERNEL_WIDE_FUSED = 12
 KERNEL_WIDE_FUSED64 = 13
@@ -177,6 +181,14 @@ def load():
     lib.rayen_wide_fused_bwd_workspace_bytes.argtypes = [p, i64]
     lib.rayen_ray_project_wide_fused_bwd_f32.restype = ctypes.c_int
     lib.rayen_ray_project_wide_fused_bwd_f32.argtypes = [p, p, i64, i64, p, i32p, p, i64, p, i64, p, i64, p]
+    lib.rayen_wide_fused_bwd64_served.restype = ctypes.c_int
+    lib.rayen_wide_fused_bwd64_served.argtypes = [p]
+    lib.rayen_wide_fused_bwd64_plan.restype = ctypes.c_int
+    lib.rayen_wide_fused_bwd64_plan.argtypes = [p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    lib.rayen_wide_fused_bwd64_workspace_bytes.restype = ctypes.c_int64
+    lib.rayen_wide_fused_bwd64_workspace_bytes.argtypes = [p, i64]
+    lib.rayen_ray_project_wide_fused_bwd_f64.restype = ctypes.c_int
+    lib.rayen_ray_project_wide_fused_bwd_f64.argtypes = [p, p, i64, i64, p, i32p, p, i64, p, i64, p, i64, ctypes.c_int32, p]
     lib.rayen_products_rows.restype = ctypes.c_int64
     lib.rayen_products_rows.argtypes = [p]
     lib.rayen_products_served.restype = ctypes.c_int

@@ -112,7 +112,8 @@ class ConstraintModule(torch.nn.Module):
         # the backward of the same sets, chosen independently (it consumes kappa and active of whichever forward made them):
         # 'products' (the default: two library GEMMs around the coefficient kernel of rayen_wide.hip) or 'fused'
         # (rayen_wide_fused_bwd.hip: one launch over the active constraints' rows; fp32, no LMI, n <= 1024 -- anything else
-        # takes the backward's loud path, ops._bwd_or_detour).  No 'auto' here either.
+        # takes the backward's loud path, ops._bwd_or_detour) or 'fused64' (its fp64 twin, rayen_wide_fused_bwd64.hip: fp64
+        # input, no LMI, n <= 1024 -- anything else likewise).  No 'auto' here either.
         self.wide_backward = wide_backward
         if bar_kernel not in self.BAR_KERNELS:
             raise ValueError(f"bar_kernel must be one of {self.BAR_KERNELS}, got {bar_kernel!r}")

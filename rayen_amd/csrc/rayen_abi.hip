@@ -2,6 +2,7 @@
 #include "rayen_internal.h"
 #include "rayen_pair_image.h"
 #include "rayen_wide_fused64_layout.h"
+#include "rayen_wide_fused_bwd64_layout.h"
 
 #include <atomic>
 #include <cmath>
@@ -822,6 +823,7 @@ void rayen_pack_destroy(RayenPack* p) {
   if (p->wf32) wide_fused_free(p->wf32);
   if (p->wfb32) wide_fused_bwd_free(p->wfb32);
   if (p->wf64) wide_fused64_free(p->wf64);
+  if (p->wfb64) wide_fused_bwd64_free(p->wfb64);
   if (p->q32) lmi_quad_free(p->q32);
   if (p->w32) lmi_wave_free(p->w32);
   if (p->w64) lmi_wave_free(p->w64);
@@ -963,6 +965,34 @@ int rayen_ray_project_wide_fused_bwd_f32(const RayenPack* p, const float* v, int
   if (rc) return rc;
   return wide_fused_backward(p, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, workspace, workspace_bytes,
                              static_cast<hipStream_t>(stream));
+}
+
+int rayen_wide_fused_bwd64_served(const RayenPack* p) { return (p != nullptr && wide_fused_bwd64_served(p)) ? 1 : 0; }
+
+int rayen_wide_fused_bwd64_plan(const RayenPack* p, int32_t samples, int64_t* out) {
+  if (p == nullptr || out == nullptr || (samples != 0 && samples != 16 && samples != 32)) return RAYEN_E_BAD_ARG;
+  WideFusedBwd64Plan pl;
+  if (!wide_fused_bwd64_plan_of(p, samples, &pl)) return RAYEN_E_UNSUPPORTED;
+  const int64_t vals[11] = {pl.kp, pl.ks, pl.ke, pl.gs, pl.rp, pl.ts, pl.np, pl.samples, pl.region_words, pl.lds_bytes,
+                            pl.served};
+  for (int i = 0; i < 11; ++i) out[i] = vals[i];
+  return RAYEN_OK;
+}
+
+int64_t rayen_wide_fused_bwd64_workspace_bytes(const RayenPack* p, int64_t B) {
+  return (p == nullptr || B <= 0) ? 0 : wide_fused_bwd64_workspace_bytes(p, B);
+}
+
+int rayen_ray_project_wide_fused_bwd_f64(const RayenPack* p, const double* v, int64_t B, int64_t ldv, const double* kappa,
+                                         const int32_t* active, const double* grad_y, int64_t ldg, double* grad_v, int64_t ldgv,
+                                         void* workspace, int64_t workspace_bytes, int32_t samples, void* stream) {
+  if (p == nullptr || B < 0 || ldv < p->n || ldg < p->k || ldgv < p->n) return RAYEN_E_BAD_ARG;
+  if (B > 0 && (!v || !kappa || !active || !grad_y || !grad_v)) return RAYEN_E_BAD_ARG;
+  if (B > ((int64_t)1 << 31) - 32 || (samples != 0 && samples != 16 && samples != 32)) return RAYEN_E_BAD_ARG;
+  const int rc = check_ready<double>(p, false);
+  if (rc) return rc;
+  return wide_fused_bwd64_backward(p, v, B, ldv, kappa, active, grad_y, ldg, grad_v, ldgv, workspace, workspace_bytes, samples,
+                                   static_cast<hipStream_t>(stream));
 }
 
 static int project_f32(const RayenPack* p, const float* v, int64_t B, int64_t ldv, float* y, int64_t ldy,

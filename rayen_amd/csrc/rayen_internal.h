@@ -67,12 +67,14 @@ struct WideFusedImage;  // rayen_wide_fused_common.h
 struct WideFusedBwdImage;  // rayen_wide_fused_bwd.hip
 struct WideFused64Image;   // rayen_wide_fused64.hip
 struct WideFused64Plan;    // rayen_wide_fused64_layout.h
+struct WideFusedBwd64Image;  // rayen_wide_fused_bwd64.hip
+struct WideFusedBwd64Plan;   // rayen_wide_fused_bwd64_layout.h
 
 }  // namespace rayen
 
 // Immutable after rayen_pack_create returns (every device image is built there), so it is shared by threads and
-// streams without a lock -- but for `wf32`, `wfb32` and `wf64`, the images of the opt-in fused wide forwards and backward, which their
-// first calls build under a lock of their own (rayen_wide_fused_common.h).
+// streams without a lock -- but for `wf32`, `wfb32`, `wf64` and `wfb64`, the images of the opt-in fused wide forwards and backwards,
+// which their first calls build under a lock of their own (rayen_wide_fused_common.h).
 struct RayenPack {
   int device = -1;
   int k = 0, n = 0, n_rows = 0;
@@ -119,6 +121,9 @@ struct RayenPack {
   // the fp64 fused wide forward's image (rayen_wide_fused64.hip), lazy in the same way and under the same lock
   mutable rayen::WideFused64Image* wf64 = nullptr;
   mutable int wf64_state = 0;
+  // the fp64 fused wide backward's images (rayen_wide_fused_bwd64.hip), likewise (it shares wf64's W where that exists)
+  mutable rayen::WideFusedBwd64Image* wfb64 = nullptr;
+  mutable int wfb64_state = 0;
   double check_split = -1.0, check_exact = -1.0, check_pair = -1.0;  // worst row errors against fp64 (fp32_selfcheck)
   // [linear rows, quadratics, cones] + ONE LMI the lane kernels do not hold: the lane kernel evaluates everything but the
   // LMI (generic image built with skip_lmi), the workgroup-per-sample kernel the LMI on top of that (rayen_abi.hip)
@@ -161,6 +166,16 @@ void wide_fused_bwd_free(WideFusedBwdImage* img);
 int wide_fused_backward(const RayenPack* p, const float* v, int64_t B, int64_t ldv, const float* kappa, const int32_t* active,
                         const float* grad_y, int64_t ldg, float* grad_v, int64_t ldgv, void* workspace, int64_t workspace_bytes,
                         hipStream_t stream);
+
+// the same in fp64 (rayen_wide_fused_bwd64.hip): no LMI, n <= 1024, a tile of 32 or 16 samples (`samples`; 0: the plan's
+// choice) within LDS.  wide_fused_bwd64_plan_of: the plan for `samples` (false: the pack has no plan -- null, or an LMI)
+bool wide_fused_bwd64_served(const RayenPack* p);
+bool wide_fused_bwd64_plan_of(const RayenPack* p, int samples, WideFusedBwd64Plan* plan);
+int64_t wide_fused_bwd64_workspace_bytes(const RayenPack* p, int64_t B);
+void wide_fused_bwd64_free(WideFusedBwd64Image* img);
+int wide_fused_bwd64_backward(const RayenPack* p, const double* v, int64_t B, int64_t ldv, const double* kappa,
+                              const int32_t* active, const double* grad_y, int64_t ldg, double* grad_v, int64_t ldgv,
+                              void* workspace, int64_t workspace_bytes, int samples, hipStream_t stream);
 
 // SIMDs the persistent grids may fill: all of the device's minus rayen_reserve_cus() compute units (a collective that
 // runs beside the projection -- RCCL's all-gather kernels in the multi-GPU step -- needs CUs of its own)

@@ -19,30 +19,10 @@
 //
 // Reductions, masks, scratch, the final pass and the treatment of y are those of rayen_wide_fused.hip on doubles: see
 // there.  Rows outside a segment are masked arithmetically with 64-bit words.
-#include "rayen_internal.h"
-#include "rayen_wide_fused64_layout.h"
-#include "rayen_wide_fused_common.h"
+// (the image, the MFMA macro and block_product<NC>: rayen_wide_fused64_common.h, shared with rayen_wide_fused_bwd64.hip)
+#include "rayen_wide_fused64_common.h"
 
 namespace rayen {
-
-struct F64Seg {   // 56 bytes
-  int32_t type, row0, nrows, aux_row;
-  int32_t first_block, last_block, wave_first, wave_last;
-  int32_t part_off, aux_off;
-  double f0, f1;
-};
-
-struct WideFused64Image {
-  double* W = nullptr;            // [rows_pad][kp]
-  double* y0 = nullptr;           // [k]
-  F64Seg* segs[2] = {nullptr, nullptr};      // [n_seg], scratch offsets of S = 16 | 32
-  int32_t* item_start = nullptr;  // [nb_w + 1]
-  FItem* items = nullptr;
-  int n_seg = 0;
-  int n_simd = 1024;
-  WideFused64Plan plan[2];        // S = 16 | 32
-  int64_t bytes = 0;
-};
 
 namespace {
 
@@ -51,9 +31,6 @@ constexpr int kMinWaves = 2;       // waves a SIMD the instances are compiled fo
 // workgroups a CU holds at most, by the registers of the instances of S (<= 102 VGPRs at S = 16,
 // <= 142 at S = 32, of 512 a SIMD)
 constexpr int per_cu_max(const int S) { return S == 16 ? 4 : 3; }
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 struct Args {
   const double* W;
@@ -83,77 +60,6 @@ __device__ __forceinline__ void lin_merge(double& m, int& at, const double bm, c
   const bool lower = bat >= 0 && (at < 0 || bat < at);
   const bool take = (bm != bm) ? (!(m != m) || lower) : (bm > m || (bm == m && lower));
   if (take) { m = bm; at = bat; }
-}
-
-#define RAYEN_WF64_MFMA2(A, Bv, ACC)                                        \
-  ACC = __builtin_amdgcn_mfma_f64_16x16x4f64((A).x, (Bv).x, ACC, 0, 0, 0);  \
-  ACC = __builtin_amdgcn_mfma_f64_16x16x4f64((A).y, (Bv).y, ACC, 0, 0, 0)
-
-// 16 rows of the image x NC column blocks of the tile: `arow` = this lane's row at its lane group's k offset, `brow` = its
-// sample of column block 0 likewise (column block c: + 16 c ks).  Chunks of four groups (32 k): the pieces of W of chunk
-// c + 1 are in flight while the MFMAs of chunk c run; what is left of K beyond whole chunks (at most three groups) follows
-// one group at a time.  Groups alternate between the two chains of every column block; out = even chain + odd chain.
-template <int NC>
-__device__ __forceinline__ void block_product(const double* __restrict__ arow, const double* brow, const int ks,
-                                              const int groups, f64x4 (&out)[NC]) {
-  f64x4 acc[NC][2];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[c][h][i] = 0.0;
-  const int chunks = groups >> 2;
-  if (chunks > 0) {
-    f64x2 a[4], an[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) a[g] = *reinterpret_cast<const f64x2*>(arow + 8 * g);
-    for (int ch = 0; ch + 1 < chunks; ++ch) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) an[g] = *reinterpret_cast<const f64x2*>(arow + 32 * (ch + 1) + 8 * g);
-      f64x2 b[NC][4];
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) b[c][g] = *reinterpret_cast<const f64x2*>(brow + 16 * c * ks + 32 * ch + 8 * g);
-      __builtin_amdgcn_sched_barrier(0);        // (the scheduler otherwise sinks the loads to their use: no prefetch left)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { RAYEN_WF64_MFMA2(a[g], b[c][g], acc[c][g & 1]); }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) a[g] = an[g];
-    }
-    f64x2 b[NC][4];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) b[c][g] = *reinterpret_cast<const f64x2*>(brow + 16 * c * ks + 32 * (chunks - 1) + 8 * g);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) { RAYEN_WF64_MFMA2(a[g], b[c][g], acc[c][g & 1]); }
-  }
-  for (int g = 4 * chunks; g < groups; ++g) {
-    const f64x2 a = *reinterpret_cast<const f64x2*>(arow + 8 * g);
-    if (g & 1) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const f64x2 b = *reinterpret_cast<const f64x2*>(brow + 16 * c * ks + 8 * g);
-        RAYEN_WF64_MFMA2(a, b, acc[c][1]);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const f64x2 b = *reinterpret_cast<const f64x2*>(brow + 16 * c * ks + 8 * g);
-        RAYEN_WF64_MFMA2(a, b, acc[c][0]);
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[c][i] = acc[c][0][i] + acc[c][1][i];
 }
 
 // WANT_Y: a.y != nullptr; IDENTITY: NA_E = I; S: samples of a tile (instances, so that none is a predicate the loops carry)
@@ -413,13 +319,7 @@ int image_build(const RayenPack* p, WideFused64Image** out) {
   (void)shape_plan(p, 32, &img->plan[1], &sp[1]);
   img->n_seg = (int)p->segs.size();
   img->n_simd = device_simds(p->device, 1024);
-  const int kp = plan16.kp, n = p->n;
-  std::vector<double> W((size_t)plan16.rows_pad * kp, 0.0);
-  for (int r = 0; r < p->n_rows; ++r)
-    for (int j = 0; j < n; ++j) W[(size_t)r * kp + j] = p->W[(size_t)r * n + j];
-  if (!p->out_identity)
-    for (int r = 0; r < p->k; ++r)
-      for (int j = 0; j < n; ++j) W[((size_t)plan16.rows_w_pad + r) * kp + j] = p->NA_E[(size_t)r * n + j];
+  const std::vector<double> W = wide_fused64_rows_image(p, plan16.rows_w_pad, plan16.rows_pad, plan16.kp);
   std::vector<F64Seg> segs[2];
   std::vector<std::vector<FItem>> per_block((size_t)plan16.nb_w);
   for (size_t i = 0; i < p->segs.size(); ++i) {

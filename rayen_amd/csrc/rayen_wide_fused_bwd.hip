@@ -21,14 +21,16 @@
 //   A row of grad_v is final when the workgroup leaves the tile; each of its words is read-modified-written at most once.
 // The gradient bits of a sample depend on the set and that sample's inputs alone: not on its tile-mates, B, or `perm`.
 //
-// Grouping by active constraint: `perm` (tile t serves samples perm[32 t ..]) comes from three small launches here -- count,
-// scan, scatter over the keys of rayen_wide_fused_bwd_layout.h -- into the caller's workspace; no allocation, no host
-// synchronisation, any number of segments.  Order inside a bucket is whatever the atomics give (no bit depends on it).
+// Grouping by active constraint: `perm` (tile t serves samples perm[32 t ..]) comes from three small launches -- count,
+// scan, scatter over the keys of rayen_wide_fused_bwd_layout.h, in rayen_wide_fused_bwd_group.h (one source with the fp64
+// backward) -- into the caller's workspace; no allocation, no host synchronisation, any number of segments.  Order inside a
+// bucket is whatever the atomics give (no bit depends on it).
 //
 // Guards: an `active` record outside the segment table, a linear row outside its segment, !(kappa > 1) (NaN included) give
 // s u alone; every row index of an image is clamped to the image.
 #include "rayen_wide_fused_common.h"
 #include "rayen_wide_fused_bwd_layout.h"
+#include "rayen_wide_fused_bwd_group.h"
 
 namespace rayen {
 
@@ -273,82 +275,6 @@ __global__ __launch_bounds__(kThreads, 3) void wide_fused_bwd_kernel(const BArgs
   }
 }
 
-// ---- grouping by active constraint: count, scan, scatter ----
-
-__device__ __forceinline__ int key_of(const BSeg* __restrict__ segs, const int n_seg, const float kap, const int ag) {
-  if (!(kap > 1.0f) || ag < 0 || ag >= n_seg) return 0;
-  return segs[ag].key;
-}
-
-// (both passes over the batch: ONE atomic per wave and distinct key in it -- a batch is a few keys, and an atomic per row
-// on so few addresses took longer than the backward itself)
-__global__ __launch_bounds__(256) void bwd_count_kernel(const BSeg* __restrict__ segs, int n_seg, const float* __restrict__ kappa,
-                                                        const int32_t* __restrict__ active, int64_t B, int32_t* cursors) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t b0 = (int64_t)blockIdx.x * 256; b0 < B; b0 += (int64_t)gridDim.x * 256) {
-    const int64_t b = b0 + threadIdx.x;
-    const int key = b < B ? key_of(segs, n_seg, kappa[b], active[2 * b]) : 0;
-    unsigned long long todo = __ballot(key > 0);             // (key 0 is what is left: it starts at 0)
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int k0 = __shfl(key, leader, 64);
-      const unsigned long long same = __ballot(key == k0);
-      if (lane == leader) atomicAdd(cursors + k0, __popcll(same));
-      todo &= ~same;
-    }
-  }
-}
-
-// counts -> first positions, by ONE workgroup (rayen_wide_fused_bwd_layout.h::wide_fused_bwd_scan restates it); key 0's count
-// is B minus the others'
-__global__ __launch_bounds__(256) void bwd_scan_kernel(int32_t* cursors, int64_t n_keys, int64_t B) {
-  __shared__ int64_t sums[256];
-  const int t = threadIdx.x;
-  const int64_t chunk = (n_keys + 255) / 256;
-  const int64_t i0 = chunk * t, i1 = (chunk * (t + 1) < n_keys) ? chunk * (t + 1) : n_keys;
-  int64_t sum = 0;
-  for (int64_t i = i0 > 0 ? i0 : 1; i < i1; ++i) sum += cursors[i];
-  sums[t] = sum;
-  __syncthreads();
-  if (t == 0) {
-    int64_t total = 0;
-    for (int w = 0; w < 256; ++w) total += sums[w];
-    int64_t base = B - total;                              // key 0's count: thread 0's chunk starts behind it
-    for (int w = 0; w < 256; ++w) { const int64_t s = sums[w]; sums[w] = base; base += s; }
-  }
-  __syncthreads();
-  int64_t at = sums[t];
-  for (int64_t i = i0; i < i1; ++i) {
-    if (i == 0) { cursors[0] = 0; continue; }
-    const int32_t c = cursors[i];
-    cursors[i] = (int32_t)at;
-    at += c;
-  }
-}
-
-__global__ __launch_bounds__(256) void bwd_scatter_kernel(const BSeg* __restrict__ segs, int n_seg, const float* __restrict__ kappa,
-                                                          const int32_t* __restrict__ active, int64_t B, int32_t* cursors,
-                                                          int32_t* __restrict__ perm) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t b0 = (int64_t)blockIdx.x * 256; b0 < B; b0 += (int64_t)gridDim.x * 256) {
-    const int64_t b = b0 + threadIdx.x;
-    const int key = b < B ? key_of(segs, n_seg, kappa[b], active[2 * b]) : -1;
-    unsigned long long todo = __ballot(key >= 0);
-    int at = -1;
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int k0 = __shfl(key, leader, 64);
-      const unsigned long long same = __ballot(key == k0);
-      int base = 0;
-      if (lane == leader) base = atomicAdd(cursors + k0, __popcll(same));
-      base = __shfl(base, leader, 64);
-      if (key == k0) at = base + __popcll(same & ((1ull << lane) - 1ull));
-      todo &= ~same;
-    }
-    if (at >= 0 && at < B) perm[at] = (int32_t)b;
-  }
-}
-
 bool shape_served(const RayenPack* p, WideFusedBwdPlan* plan) {
   if (p == nullptr || p->wide == nullptr) return false;            // (no tables: the set has an LMI)
   int widest = 0;
@@ -479,21 +405,11 @@ int wide_fused_backward(const RayenPack* p, const float* v, int64_t B, int64_t l
   }
   if (B == 0) return RAYEN_OK;
   const WideFusedBwdPlan& pl = img->plan;
-  // the permutation, where the caller brought room for it
+  // the permutation, where the caller brought room for it (rayen_wide_fused_bwd_group.h)
   const int32_t* perm = nullptr;
-  const int64_t need = wide_fused_bwd_workspace(img->n_nl, B);
-  if (workspace != nullptr && need > 0 && workspace_bytes >= need) {
-    const int64_t n_keys = (int64_t)img->n_nl + 1;
-    int32_t* cursors = static_cast<int32_t*>(workspace);
-    int32_t* pm = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + wide_fused_bwd_perm_offset(n_keys));
-    if (hipMemsetAsync(cursors, 0, (size_t)(4 * n_keys), stream) != hipSuccess) return RAYEN_E_LAUNCH;
-    const int64_t want = (B + 255) / 256, cap = (int64_t)launch_simds(img->n_simd);
-    const unsigned g = (unsigned)(want < cap ? want : cap);
-    hipLaunchKernelGGL(bwd_count_kernel, dim3(g), dim3(256), 0, stream, img->segs, img->n_seg, kappa, active, B, cursors);
-    hipLaunchKernelGGL(bwd_scan_kernel, dim3(1), dim3(256), 0, stream, cursors, n_keys, B);
-    hipLaunchKernelGGL(bwd_scatter_kernel, dim3(g), dim3(256), 0, stream, img->segs, img->n_seg, kappa, active, B, cursors, pm);
-    perm = pm;
-  }
+  if (!bwd_group<float, BSeg>(img->segs, img->n_seg, img->n_nl, img->n_simd, kappa, active, B, workspace, workspace_bytes,
+                              stream, &perm))
+    return RAYEN_E_LAUNCH;
   BArgs a;
   a.W = img->W; a.Wt = img->Wt; a.Et = img->Et; a.segs = img->segs;
   a.n_seg = img->n_seg; a.n = p->n; a.k = p->k; a.kp = pl.kp; a.ks = pl.ks; a.ke = pl.ke; a.gs = pl.gs; a.ts = pl.ts;

@@ -270,11 +270,18 @@ def _(v, pack_id, need_active):
             v.new_empty((B if need_active else 0, 2), dtype=torch.int32))
 
 
-WIDE_BACKWARDS = ('products', 'fused')
+WIDE_BACKWARDS = ('products', 'fused', 'fused64')
+# the fused wide backwards: route -> (dtype it serves, workspace query, entry point, takes `wide_samples`, name in errors)
+_WIDE_FUSED_BWD = {
+    'fused': (torch.float32, "rayen_wide_fused_bwd_workspace_bytes", "rayen_ray_project_wide_fused_bwd_f32", False,
+              "rayen_ray_project_wide_fused_bwd"),
+    'fused64': (torch.float64, "rayen_wide_fused_bwd64_workspace_bytes", "rayen_ray_project_wide_fused_bwd_f64", True,
+                "rayen_ray_project_wide_fused_bwd64"),
+}
 
 
 def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=False, bucketed=True,
-                 wide_backward='products', group=True):
+                 wide_backward='products', group=True, wide_samples=0):
     """Direct call of the backward entry points; ``force_generic`` pins the lane-per-sample kernel
     where ``rayen_ray_project_bwd_f32/_f64`` would pick the matrix-core one.  ``bucketed``: hand the library the
     scratch buffer it asks for (``rayen_bwd_workspace_bytes_f32``) so that it may group the samples by active
@@ -282,9 +289,12 @@ def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=F
     ``wide_backward``: what serves a call that takes the wide route (``_wide_route``): ``'products'`` -- two library GEMMs
     around the coefficient kernel of rayen_wide.hip -- or ``'fused'`` -- ``rayen_ray_project_wide_fused_bwd_f32``
     (rayen_wide_fused_bwd.hip): one launch over the active constraints' rows, neither T nor C; fp32, no LMI, n <= 1024,
-    anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on a call that does not take the wide route.  ``group``
-    (developer flag of the fused route): hand the library the workspace with which it groups the rows by active constraint;
-    ``False`` pins batch order (same bits)."""
+    anything else is ``RAYEN_E_UNSUPPORTED`` -- or ``'fused64'`` -- its fp64 twin ``rayen_ray_project_wide_fused_bwd_f64``
+    (rayen_wide_fused_bwd64.hip): fp64, no LMI, n <= 1024, anything else is ``RAYEN_E_UNSUPPORTED``.  No effect on a call
+    that does not take the wide route.  ``group`` (developer flag of the fused routes): hand the library the workspace with
+    which it groups the rows by active constraint; ``False`` pins batch order (same bits).  ``wide_samples`` (tests and
+    measurements): the sample tile of ``'fused64'``, 16 or 32; 0 leaves it to the plan.  The bits of a row do not depend on
+    it."""
     if wide_backward not in WIDE_BACKWARDS:
         raise ValueError(f"wide_backward must be one of {WIDE_BACKWARDS}, got {wide_backward!r}")
     _check_input(v, pack)
@@ -300,18 +310,21 @@ def backward_raw(v, kappa, active, grad_y, pack, old_head=False, force_generic=F
             raise RuntimeError("force_generic selects between the two RAYEN backward kernels only")
         name = "rayen_ray_project_bwd_generic_f32" if v.dtype == torch.float32 else "rayen_ray_project_bwd_generic_f64"
     Wt = _wide_route(v, pack, force_generic, old_head) if B else None
-    if Wt is not None and wide_backward == 'fused':
+    if Wt is not None and wide_backward in _WIDE_FUSED_BWD:
+        # one launch over the active constraints' rows: each route serves its own precision alone
+        dtype, ws_fn, entry, takes_samples, what = _WIDE_FUSED_BWD[wide_backward]
         with _on_device(v.device):
-            if v.dtype != torch.float32:
-                code = _lib.E_UNSUPPORTED        # (the fused kernel is fp32 only: rayen_wide_fused_bwd_served(pack, 1) == 0)
+            if v.dtype != dtype:
+                code = _lib.E_UNSUPPORTED        # ('fused' is fp32 only, 'fused64' fp64 only)
             else:
                 lib = _lib.load()
-                ws_bytes = int(lib.rayen_wide_fused_bwd_workspace_bytes(pack.handle, B)) if group else 0
+                ws_bytes = int(getattr(lib, ws_fn)(pack.handle, B)) if group else 0
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device) if ws_bytes > 0 else None   # (caching allocator)
-                code = lib.rayen_ray_project_wide_fused_bwd_f32(
+                tile = (int(wide_samples),) if takes_samples else ()
+                code = getattr(lib, entry)(
                     pack.handle, _ptr(v), B, v.stride(0), _ptr(kappa), _ptr(active), _ptr(grad_y), grad_y.stride(0),
-                    _ptr(grad_v), grad_v.stride(0), _ptr(ws), ws_bytes, _stream(v.device.index))
-        _lib.check(code, "rayen_ray_project_wide_fused_bwd")
+                    _ptr(grad_v), grad_v.stride(0), _ptr(ws), ws_bytes, *tile, _stream(v.device.index))
+        _lib.check(code, what)
         return grad_v
     if Wt is not None:
         # wide sets: T = v W_ext' again (one GEMM), the coefficient kernel, grad_v = C W_ext (+ s g): rayen_wide.hip
@@ -360,11 +373,14 @@ def _bwd_or_detour(v, kappa, active, grad_y, pack_id, old_head, wide_backward='p
     """The HIP backward; where the kernels decline the shape (``RAYEN_E_UNSUPPORTED``), autograd through the packed
     torch evaluator on the same device -- loudly, once per pack and route.  Called from the autograd formulas (NOT from
     inside the custom op: below the dispatcher's autograd key nothing would be recorded).  A refusal of
-    ``wide_backward='fused'`` is remembered per dtype: later calls go to the evaluator without asking again."""
-    fused = wide_backward == 'fused'
-    if fused and (v.dtype, 'fused') in _pack(pack_id).__dict__.get("_refused_bwd", ()):
+    ``wide_backward='fused'`` or ``'fused64'`` is remembered per dtype and route: later calls go to the evaluator without
+    asking again."""
+    fused = wide_backward in ('fused', 'fused64')
+    if fused and (v.dtype, wide_backward) in _pack(pack_id).__dict__.get("_refused_bwd", ()):
         return _eager_backward(_pack(pack_id), v, grad_y, old_head)
     try:
+        if wide_backward == 'fused64':
+            return torch.ops.rayen_amd.ray_project_bwd_wide_fused64(v, kappa, active, grad_y, pack_id)
         if fused:
             return torch.ops.rayen_amd.ray_project_bwd_wide_fused(v, kappa, active, grad_y, pack_id)
         return torch.ops.rayen_amd.ray_project_bwd(v, kappa, active, grad_y, pack_id, old_head)
@@ -372,14 +388,14 @@ def _bwd_or_detour(v, kappa, active, grad_y, pack_id, old_head, wide_backward='p
         if err.code != _lib.E_UNSUPPORTED or os.environ.get("RAYEN_STRICT_HIP", "0") == "1":
             raise
         pack = _pack(pack_id)
-        warned = "_warned_bwd_wide_fused" if fused else "_warned_bwd"
+        warned = "_warned_bwd_wide_" + wide_backward if fused else "_warned_bwd"
         if not pack.__dict__.get(warned):
             warnings.warn(f"rayen_amd: no HIP backward kernel serves this constraint set ({err}); gradients come from "
                           "autograd through the packed torch evaluator (rayen_amd/eager.py) on " + str(v.device),
                           RuntimeWarning, stacklevel=2)
             pack.__dict__[warned] = True
         if fused:
-            pack.__dict__.setdefault("_refused_bwd", set()).add((v.dtype, 'fused'))
+            pack.__dict__.setdefault("_refused_bwd", set()).add((v.dtype, wide_backward))
         return _eager_backward(pack, v, grad_y, old_head)
 
 
@@ -447,11 +463,24 @@ def _(v, kappa, active, grad_y, pack_id):
     return torch.empty_like(v)
 
 
+@torch.library.custom_op("rayen_amd::ray_project_bwd_wide_fused64", mutates_args=())
+def ray_project_bwd_wide_fused64(v: torch.Tensor, kappa: torch.Tensor, active: torch.Tensor, grad_y: torch.Tensor,
+                                 pack_id: int) -> torch.Tensor:
+    """``rayen_amd::ray_project_bwd`` with ``wide_backward='fused64'``: wide sets in fp64 on rayen_wide_fused_bwd64.hip (a
+    call that does not take the wide route runs what ``ray_project_bwd`` runs)."""
+    return backward_raw(v, kappa, active, grad_y, _pack(pack_id), wide_backward='fused64')
+
+
+@ray_project_bwd_wide_fused64.register_fake
+def _(v, kappa, active, grad_y, pack_id):
+    return torch.empty_like(v)
+
+
 @torch.library.custom_op("rayen_amd::ray_project_wide", mutates_args=())
 def ray_project_wide(v: torch.Tensor, pack_id: int, need_active: bool, wide_kernel: str,
                      wide_backward: str) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``rayen_amd::ray_project`` with both choices of the wide route spelled out: the forward by ``wide_kernel``, the
-    backward (``rayen_amd::ray_project_bwd`` or ``rayen_amd::ray_project_bwd_wide_fused``) by ``wide_backward`` -- it consumes
+    backward (``rayen_amd::ray_project_bwd``, ``rayen_amd::ray_project_bwd_wide_fused`` or ``..._wide_fused64``) by ``wide_backward`` -- it consumes
     ``kappa`` and ``active`` of whichever forward made them."""
     if wide_backward not in WIDE_BACKWARDS:
         raise ValueError(f"wide_backward must be one of {WIDE_BACKWARDS}, got {wide_backward!r}")
