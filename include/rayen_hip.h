@@ -556,6 +556,9 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 /* ---- ... and its backward in fp64 (additive to ABI v15) */
 #include "rayen_hip_wide_fused_bwd64.h"
 
+/* ---- The soft cost in fp64 on the fp64 matrix cores, opt-in (additive to ABI v15) */
+#include "rayen_hip_cost_tile64.h"
+
 #ifdef __cplusplus
 }
 #endif

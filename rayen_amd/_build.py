@@ -16,6 +16,7 @@ SOURCES = ["rayen_abi.hip", "rayen_generic.hip", "rayen_mfma.hip", "rayen_mfma_s
            "rayen_lmi_quad32.hip", "rayen_lmi_quad64.hip", "rayen_bar.hip", "rayen_dc3.hip", "rayen_proj.hip", "rayen_cost.hip", "rayen_cost_lmi.hip", "rayen_proj_tile.hip", "rayen_dc3_tile.hip",
            "rayen_cost_stream.hip", "rayen_bar_stream.hip", "rayen_wide_fused.hip", "rayen_wide_fused_bwd.hip",
            "rayen_dc3_tile64.hip", "rayen_proj_tile64.hip", "rayen_wide_fused64.hip", "rayen_wide_fused_bwd64.hip",
+           "rayen_cost_tile64.hip",
            "rayen_pair_image.hip"]     # host code only (no kernel); last, so the kernel sources' code objects keep their order
 # On gfx950 a packed-fp32 instruction whose low result reads the HIGH half of its second source (op_sel:[0,1,..]: how hipcc's
 # SLP vectoriser broadcasts the second element of a register pair) reads that operand as 0 in lanes 48-63 now and then while
@@ -44,7 +45,8 @@ EXTRA_FLAGS = {"rayen_generic.hip": ["-fno-slp-vectorize"],          # per-sourc
                "rayen_wide_fused.hip": ["-fno-slp-vectorize"],      # (executes MFMAs next to its own vector arithmetic)
                "rayen_wide_fused_bwd.hip": ["-fno-slp-vectorize"],  # (likewise)
                "rayen_wide_fused64.hip": ["-fno-slp-vectorize"],    # (likewise)
-               "rayen_wide_fused_bwd64.hip": ["-fno-slp-vectorize"]}  # (likewise)
+               "rayen_wide_fused_bwd64.hip": ["-fno-slp-vectorize"],  # (likewise)
+               "rayen_cost_tile64.hip": ["-fno-slp-vectorize"]}       # (likewise)
 LIBRARY = os.environ.get("RAYEN_HIP_LIBRARY") or os.path.join(CSRC, "librayen_hip.so")
 
 
@@ -62,7 +64,7 @@ def is_stale():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
     deps += [os.path.join(INCLUDE, f) for f in ("rayen_hip.h", "rayen_hip_tile.h", "rayen_hip_tile64.h", "rayen_hip_dc3_tile.h", "rayen_hip_dc3_tile64.h", "rayen_hip_cost_stream.h",
                                                 "rayen_hip_bar_stream.h", "rayen_hip_wide_fused.h", "rayen_hip_wide_fused_bwd.h",
-                                                "rayen_hip_wide_fused64.h", "rayen_hip_wide_fused_bwd64.h")]
+                                                "rayen_hip_wide_fused64.h", "rayen_hip_wide_fused_bwd64.h", "rayen_hip_cost_tile64.h")]
     return any(os.path.getmtime(d) > built for d in deps)
 
 

@@ -77,6 +77,9 @@ EXPORTS_WIDE_FUSED64 = ("rayen_wide_fused64_served", "rayen_wide_fused64_plan", 
 # tests/test_wide_fused_bwd64_host.py holds the two against each other
 EXPORTS_WIDE_FUSED_BWD64 = ("rayen_wide_fused_bwd64_served", "rayen_wide_fused_bwd64_plan",
                             "rayen_wide_fused_bwd64_workspace_bytes", "rayen_ray_project_wide_fused_bwd_f64")
+# additive to ABI v15, declared in include/rayen_hip_cost_tile64.h (which rayen_hip.h includes, like the eight above);
+# tests/test_cost_tile64_host.py holds the two against each other
+EXPORTS_COST_TILE64 = ("rayen_cost_tile64_set", "rayen_cost_tile64_served", "rayen_soft_cost_tile64_f64")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 KERNEL_WIDE_FUSED = 12
 KERNEL_WIDE_FUSED64 = 13
@@ -304,13 +307,18 @@ def load():
     lib.rayen_cost_pack_destroy.argtypes = [p]
     lib.rayen_cost_served.restype = ctypes.c_int
     lib.rayen_cost_served.argtypes = [p, i32]
-    for name in ("rayen_soft_cost_f32", "rayen_soft_cost_f64", "rayen_soft_cost_stream_f32", "rayen_soft_cost_stream_f64"):
+    for name in ("rayen_soft_cost_f32", "rayen_soft_cost_f64", "rayen_soft_cost_stream_f32", "rayen_soft_cost_stream_f64",
+                 "rayen_soft_cost_tile64_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [p, p, i64, i64, p, p, i32p, p, i64, p]
     lib.rayen_cost_stream_set.restype = ctypes.c_int
     lib.rayen_cost_stream_set.argtypes = [p, i64]
     lib.rayen_cost_stream_served.restype = ctypes.c_int
     lib.rayen_cost_stream_served.argtypes = [p, i32]
+    lib.rayen_cost_tile64_set.restype = ctypes.c_int
+    lib.rayen_cost_tile64_set.argtypes = [p, i64]
+    lib.rayen_cost_tile64_served.restype = ctypes.c_int
+    lib.rayen_cost_tile64_served.argtypes = [p]
     if lib.rayen_abi_version() != ABI_VERSION:
         raise RuntimeError(f"librayen_hip.so ABI {lib.rayen_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

@@ -31,8 +31,8 @@ class CostComputer(nn.Module):
     def __init__(self, cs, fused=False, kernel="resident"):
         """``fused=True``: ``getSumSoftCostAllSamples`` is ``rayen_amd.soft_cost.SoftCost`` summed -- on a HIP device loss and
         gradient in one launch of ``rayen_cost.hip`` -- instead of the chain of torch ops below; everything else is unchanged.
-        ``kernel`` is ``SoftCost``'s (``'resident'``, ``'stream'``, ``'auto'``) and needs ``fused=True`` for any other value
-        than the default."""
+        ``kernel`` is ``SoftCost``'s (``'resident'``, ``'stream'``, ``'auto'``, ``'tile64'``) and needs ``fused=True`` for any
+        other value than the default."""
         super().__init__()
         self.fused = bool(fused)
         from .soft_cost import KERNELS

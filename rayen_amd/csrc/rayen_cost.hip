@@ -624,6 +624,7 @@ void rayen_cost_pack_destroy(RayenCostPack* p) {
     if (p->img64) (void)hipFree(p->img64);
     rayen::cost_lmi_free(p->lmi);
     rayen::cost_stream_free(p->stream);
+    rayen::cost_tile64_free(p->tile64);
   }
   delete p;
 }

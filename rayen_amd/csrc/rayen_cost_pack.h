@@ -1,5 +1,6 @@
-// The soft-cost pack, shared by its two translation units: rayen_cost.hip (the pack, the image builders and the resident
-// kernels) and rayen_cost_stream.hip (the streamed route: windows of the same image through LDS).  Host code only.
+// The soft-cost pack, shared by its translation units: rayen_cost.hip (the pack, the image builders and the resident
+// kernels), rayen_cost_stream.hip (the streamed route: windows of the same image through LDS) and rayen_cost_tile64.hip (the
+// fp64 tile route: an image of its own in blocks of 16 rows).  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,8 @@
 namespace rayen {
 struct CostStream;      // rayen_cost_stream.hip
 void cost_stream_free(CostStream* s);
+struct CostTile64;      // rayen_cost_tile64.hip
+void cost_tile64_free(CostTile64* t);
 }  // namespace rayen
 
 struct RayenCostPack {
@@ -37,6 +40,8 @@ struct RayenCostPack {
   std::vector<int32_t> host_soc_rows;
   int m1 = 0, nq = 0, nsoc = 0, m2 = 0;
   rayen::CostStream* stream = nullptr;
+  // the fp64 tile route (rayen_cost_tile64_set): its image of the same host arrays, once somebody asked
+  rayen::CostTile64* tile64 = nullptr;
 };
 
 namespace rayen {

@@ -1387,15 +1387,26 @@ class CostPack(_SidePack):
         self._stream_set = True
         return bool(_entry("rayen_cost_stream_served")(self.handle, int(dtype == torch.float64)))
 
+    def tile64_served(self, window_bytes=0):
+        """Does the fp64 tile route (``rayen_cost_tile64.hip``: blocks of 16 stacked rows on the fp64 matrix cores, the image
+        through LDS in windows of ``window_bytes`` bytes, 0 = the default of 80 KiB) serve the set?  The first call, and every
+        call with another window size, builds and uploads the image; a pack nobody asks holds none."""
+        with torch.cuda.device(self.device_index):
+            _lib.check(_entry("rayen_cost_tile64_set")(self.handle, int(window_bytes)), "rayen_cost_tile64_set")
+        self._tile64_set = True
+        return bool(_entry("rayen_cost_tile64_served")(self.handle))
 
-COST_KERNELS = ("resident", "stream")
+
+COST_KERNELS = ("resident", "stream", "tile64")
 
 
 def soft_cost_raw(y, pack, want_grad, kernel="resident"):
     """``(cost [B], worst [B], which [B] int32, grad [B, k] | None)`` of ``y [B, >= k]`` through ``rayen_soft_cost_*``
     (``kernel='resident'``: the image of the stacked rows in LDS) or ``rayen_soft_cost_stream_*`` (``'stream'``: the image
-    through LDS in windows, at the window size of the pack's last ``stream_served`` call, the default if there was none):
-    one launch (two for a set that has an LMI next to other constraints)."""
+    through LDS in windows, at the window size of the pack's last ``stream_served`` call, the default if there was none) or
+    ``rayen_soft_cost_tile64_f64`` (``'tile64'``: blocks of 16 rows on the fp64 matrix cores, at the window size of the pack's
+    last ``tile64_served`` call; fp64 only: an fp32 call is refused with ``E_UNSUPPORTED``): one launch (two for a set that has
+    an LMI next to other constraints)."""
     if kernel not in COST_KERNELS:
         raise ValueError(f"rayen_amd: kernel must be one of {COST_KERNELS}, got {kernel!r}")
     _check_rows(y, pack.k, pack, "y", "cost")
@@ -1406,6 +1417,14 @@ def soft_cost_raw(y, pack, want_grad, kernel="resident"):
             with torch.cuda.device(pack.device_index):
                 _lib.check(_entry("rayen_cost_stream_set")(pack.handle, 0), "rayen_cost_stream_set")
             pack._stream_set = True
+    entry = None
+    if kernel == "tile64":
+        name = "rayen_soft_cost_tile64"
+        if y.dtype != torch.float64:
+            raise _lib.RayenError(_lib.E_UNSUPPORTED, name)
+        if not getattr(pack, "_tile64_set", False):
+            pack.tile64_served()
+        entry = _entry("rayen_soft_cost_tile64_f64")
     y = _dense_rows(y, pack.k)
     B = y.shape[0]
     cost = torch.empty((B,), dtype=y.dtype, device=y.device)
@@ -1413,7 +1432,7 @@ def soft_cost_raw(y, pack, want_grad, kernel="resident"):
     which = torch.empty((B,), dtype=torch.int32, device=y.device)
     grad = torch.empty((B, pack.k), dtype=y.dtype, device=y.device) if want_grad else None
     with _on_device(y.device):
-        code = _typed(name, y.dtype)(
+        code = (entry or _typed(name, y.dtype))(
             pack.handle, _ptr(y), B, y.stride(0) if B else pack.k, _ptr(cost), _ptr(worst), _ptr(which), _ptr(grad),
             pack.k, _stream(y.device.index))
     _lib.check(code, name)
@@ -1474,3 +1493,22 @@ def _(y, pack_id, need_grad):
 
 
 soft_cost_stream.register_autograd(_cost_backward, setup_context=_cost_setup_context)
+
+
+@torch.library.custom_op("rayen_amd::soft_cost_tile64", mutates_args=())
+def soft_cost_tile64(y: torch.Tensor, pack_id: int, need_grad: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rayen_amd::soft_cost`` on the fp64 tile route (``rayen_cost_tile64.hip``): the same outputs (against the lane
+    kernels the differences are summation order) and the same autograd; fp64 rows only."""
+    pack = _pack(pack_id)
+    cost, worst, which, grad = soft_cost_raw(y, pack, need_grad, kernel="tile64")
+    return cost, worst, which, (grad if grad is not None else y.new_empty((0, pack.k)))
+
+
+@soft_cost_tile64.register_fake
+def _(y, pack_id, need_grad):
+    B, k = y.shape[0], _pack(pack_id).k
+    return (y.new_empty((B,)), y.new_empty((B,)), y.new_empty((B,), dtype=torch.int32),
+            y.new_empty((B if need_grad else 0, k)))
+
+
+soft_cost_tile64.register_autograd(_cost_backward, setup_context=_cost_setup_context)

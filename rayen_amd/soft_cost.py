@@ -25,7 +25,10 @@ of the stacked rows in LDS, refused beyond 160 KiB.  ``'stream'`` runs ``rayen_a
 ``rayen_amd::soft_cost_stream``: the same image cut into windows that a workgroup brings through LDS one after another, the
 same arithmetic in the same order (bit for bit the resident result where both serve), for sets of any number of rows
 (``k <= 64``).  ``'auto'`` takes the resident kernel wherever it serves at the input's dtype, else the streamed one, else the
-mirror.  Host tensors take the mirror under every value.
+mirror.  ``'tile64'`` runs ``rayen_amd/csrc/rayen_cost_tile64.hip`` through ``rayen_amd::soft_cost_tile64``: fp64 rows in
+blocks of 16 stacked rows on the fp64 matrix cores, 32 samples per wave, the image through LDS in windows (``k <= 64``, any
+number of rows); exact fp64 in another summation order than the lane kernels.  It is fp64 only: fp32 and 16-bit device rows
+take the loud path to the mirror.  ``'auto'`` never chooses it.  Host tensors take the mirror under every value.
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ import torch.nn as nn
 
 from . import _lib
 
-KERNELS = ("resident", "stream", "auto")
+KERNELS = ("resident", "stream", "auto", "tile64")
 _NAMES = ("A1", "b1", "P", "q", "r", "M", "s", "c", "d", "A2", "b2", "F")
 
 
@@ -182,7 +185,7 @@ class SoftCost(nn.Module):
         return mirror(self.constants(y2.dtype, y2.device), y2)
 
     def _route(self, pack, dtype):
-        """``'resident'`` or ``'stream'``: the route ``kernel`` sends device rows of ``dtype`` to (sizes alone decide).
+        """``'resident'``, ``'stream'`` or ``'tile64'``: the route ``kernel`` sends device rows of ``dtype`` to (sizes alone decide).
         ``'auto'`` decides once per (device, dtype): the stream images are asked for at most once, at the default window."""
         if self.kernel != "auto":
             return self.kernel
@@ -203,7 +206,8 @@ class SoftCost(nn.Module):
             pack, pack_id = self.cost_pack(y2.device)
             route = self._route(pack, y2.dtype)
             if want_grad:
-                op = torch.ops.rayen_amd.soft_cost_stream if route == "stream" else torch.ops.rayen_amd.soft_cost
+                op = {"stream": torch.ops.rayen_amd.soft_cost_stream, "tile64": torch.ops.rayen_amd.soft_cost_tile64}.get(
+                    route, torch.ops.rayen_amd.soft_cost)
                 cost, worst, which, _ = op(y2, pack_id, True)
             else:
                 cost, worst, which, _ = ops.soft_cost_raw(y2.detach(), pack, False, kernel=route)
