@@ -188,6 +188,14 @@ int rayen_pair_screen(int mode);
  * (one atomic per wave at its exit).  Process-wide; the buffer must outlive the launches issued while it is armed. */
 int rayen_pair_screen_counters(uint32_t* device_counts);
 
+/* Tuning / A-B switch (round 9, process-wide, additive to ABI v15): progress-ordered issue priority in schedule 3 of the
+ * f16-pair forward, for calls without the fused mapper.  A SIMD serves priority first, then age; with the switch on a wave's
+ * priority goes down with every further group it claims and, inside the last group it will walk, twice more down the item
+ * list, so that the four waves of a SIMD finish together instead of one after the other (rayen_amd/csrc/rayen_mfma_pair_wl.hip,
+ * "Drain").  Same y, kappa and record bit for bit: only the order in which waves issue changes.  0 (default): off | 1: on.
+ * Initial value from RAYEN_PAIR_DRAIN.  Any other mode only queries.  Returns the previous setting. */
+int rayen_pair_drain(int mode);
+
 /* Multi-GPU step (ABI v4, process-wide): leave `cus` compute units out of the persistent grids of the projection
  * kernels, for a collective that runs beside them -- the all-gather of y that BASELINE.json's multi-GPU layout adds
  * (RCCL's kernels need CUs; a grid that fills every SIMD with resident waves serialises them behind the projection).

@@ -37,7 +37,7 @@ EXPORTS = (
     "rayen_proj_pack_create", "rayen_proj_pack_set_psd", "rayen_proj_pack_destroy", "rayen_proj_workspace_bytes", "rayen_proj_forward_f32",
     "rayen_proj_forward_f64", "rayen_proj_backward_f32", "rayen_proj_backward_f64",
     "rayen_cost_pack_create", "rayen_cost_pack_set_lmi", "rayen_cost_pack_destroy", "rayen_cost_served", "rayen_soft_cost_f32", "rayen_soft_cost_f64",
-    "rayen_pair_screen", "rayen_pair_screen_counters",
+    "rayen_pair_screen", "rayen_pair_screen_counters", "rayen_pair_drain",
 )
 # ABI v15, declared in include/rayen_hip_tile.h (which rayen_hip.h includes); tests/test_proj_tile_host.py holds the two
 # against each other
@@ -148,6 +148,9 @@ def load():
     lib.rayen_pair_screen.argtypes = [ctypes.c_int]
     lib.rayen_pair_screen_counters.restype = ctypes.c_int
     lib.rayen_pair_screen_counters.argtypes = [ctypes.c_void_p]
+    # (mode: 1 progress-ordered issue priority in schedule 3 | 0 off (default) | anything else queries)
+    lib.rayen_pair_drain.restype = ctypes.c_int
+    lib.rayen_pair_drain.argtypes = [ctypes.c_int]
     lib.rayen_reserve_cus.restype = ctypes.c_int
     lib.rayen_reserve_cus.argtypes = [ctypes.c_int]
     lib.rayen_strerror.restype = ctypes.c_char_p

@@ -144,6 +144,55 @@ __device__ __forceinline__ void wl_dma16(const char* gbase, const unsigned voff,
                : [off] "v"(voff), [base] "s"(gbase), [lds] "s"(lds)
                : "memory");
 }
+// x + (the other half's x) and max(x, the other half's x) without LDS (round 9, the instances without a mapper): one
+// v_permlane32_swap on two copies of x leaves [low half's x | low half's x] and [high half's x | high half's x]; their sum /
+// maximum is the same value in both halves and, both operations being commutative, the bits of x + xhalf(x) / fmaxf(x, xhalf(x)).
+// The ds_bpermute_b32 of xhalf forces an s_waitcnt lgkmcnt(0), which also drains the next item's A-operand reads and its record.
+// developer builds: -DRAYEN_WL_SWAP=0 keeps xhalf
+#ifndef RAYEN_WL_SWAP
+#define RAYEN_WL_SWAP 1
+#endif
+template <bool SWAP> __device__ __forceinline__ float wl_half_sum(const float x) {
+  if constexpr (SWAP && RAYEN_WL_SWAP) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+  } else {
+    return x + xhalf(x);
+  }
+}
+template <bool SWAP> __device__ __forceinline__ float wl_half_max(const float x) {
+  if constexpr (SWAP && RAYEN_WL_SWAP) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+  } else {
+    return fmaxf(x, xhalf(x));
+  }
+}
+// (SCREEN instances) the NaN / Inf flag of a row from its ||sv v||^2, which the screening decisions need anyway: the scaled entries
+// are below 2^14 and there are 64 squares, so a finite row cannot overflow, and an infinite or NaN component propagates through
+// its product and the sums -- nan_row = !(nv2 < inf) replaces the sixteen pair_nan_fold of the split and the two compares
+// (tests/test_pair_nv2_flag_host.py).  developer builds: -DRAYEN_WL_NANNV2=0 keeps pair_nan_fold
+#ifndef RAYEN_WL_NANNV2
+#define RAYEN_WL_NANNV2 1
+#endif
+// Drain (round 9; rayen_pair_drain, the instances without a mapper): the issue arbiter of a SIMD serves priority first, then age,
+// so under equal priorities the four waves of a SIMD finish their last groups one after the other and the last one walks the
+// tail alone, issuing for a third of its clocks.  With the switch on, a wave's priority follows its PROGRESS: 3 in its first
+// group, one less with every further group it claims, and inside the last group it will walk one less again a third and two
+// thirds of the way down the item list -- the wave that is behind outranks the wave that is ahead.  One s_setprio per step (the
+// priority is an immediate: a uniform branch picks it); no wave ever waits for another.
+//   Measured (profiles/bench/r09_wl_drain.txt; config 3): the waves of a SIMD do finish together -- 8.2 -> 4.5 us with three, two
+// and one of them alive at B = 262 144 -- and the launch is 1.4 % SLOWER there (1.7 % at B = 32 768): held back together, all four
+// reach their epilogues and stores at once, where the staggered finish overlaps one wave's closing vector work with the others'
+// MFMAs.  Faster only at eight groups per wave (B = 1 048 576: -2.0 % in one session).  Off by default.
+__device__ __forceinline__ void wl_set_level(const int level) {
+  if (level <= 0) __builtin_amdgcn_s_setprio(3);
+  else if (level == 1) __builtin_amdgcn_s_setprio(2);
+  else if (level == 2) __builtin_amdgcn_s_setprio(1);
+  else __builtin_amdgcn_s_setprio(0);
+}
 // the mapped instances carry the mapper's image (up to 16 KiB) next to W's: eight rows at a time through 1 KiB
 constexpr int kWlStageRowsMapped = 8;
 constexpr int wl_region_bytes_mapped(int nkk, int nt) {
@@ -173,18 +222,34 @@ extern "C" int rayen_debug_wl_stamps(void* dst, size_t bytes) {
 #else
 #define RAYEN_WL_STAMP(item, slot) do { } while (0)
 #endif
+// Round 9: the probe covers all sixteen waves of every 16th workgroup -- [workgroup / 16][wave][entry | first MFMA | end of the
+// first group | exit] x [s_memtime, s_memrealtime], then the wave's HW_ID (its SIMD) and the groups it walked
+// (scripts/ubench/wl_drain.py: how long a SIMD runs with 4, 3, 2, 1 and 0 of its waves alive).
 #ifdef RAYEN_WL_CLOCK
-__device__ unsigned long long wl_clock_buf[16 * 4];
+constexpr int kWlClockSlots = 10;
+__device__ unsigned long long wl_clock_buf[16 * 16 * kWlClockSlots];
 extern "C" int rayen_debug_wl_clock(void* dst, size_t bytes) {
   return hipMemcpyFromSymbol(dst, HIP_SYMBOL(wl_clock_buf), bytes < sizeof(wl_clock_buf) ? bytes : sizeof(wl_clock_buf)) == hipSuccess ? 0 : -1;
 }
+#define RAYEN_WL_CLOCK_AT(slot)                                               \
+  do {                                                                        \
+    if (probe) {                                                              \
+      clock_at[2 * (slot) + 0] = __builtin_amdgcn_s_memtime();                \
+      clock_at[2 * (slot) + 1] = __builtin_amdgcn_s_memrealtime();            \
+    }                                                                         \
+  } while (0)
+#else
+#define RAYEN_WL_CLOCK_AT(slot) do { } while (0)
 #endif
 
 // NKX > 0: the module's mapper v = Wm x + b in front of the walk (rayen/constraint_module.py:259-263, 525; the arithmetic of
 // rayen_mfma_pair.hip's mapped instances, bit for bit): `v` / `ldv` / `n_in` are then x, its leading dimension and its width, the
 // mapper's f16-pair image (NKK x 2 NKX K-steps x 2 pieces of 1 KiB, then bias, gM, 1 / gM: pair_mapper_image_kernel) is copied into
 // LDS behind the image of W, and v reaches memory only when v_out != null (training).
-template <int NKK, bool TRACK, int NT, int NW, int NKX = 0, bool SCREEN = false>
+// DRAIN: the instances rayen_pair_drain(1) selects ("Drain" above).  Instances of their own, not a kernel argument: with the
+// switch as an argument the walk that does NOT use it ran 1 % slower (eleven more scalar registers spilled at the group's top, a
+// compare and a branch per item; profiles/bench/r09_wl_drain.txt).
+template <int NKK, bool TRACK, int NT, int NW, int NKX = 0, bool SCREEN = false, bool DRAIN = false>
 __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     const f16x8* __restrict__ Wh, const MItem* __restrict__ items, int n_items,
     const MPack* __restrict__ packs, const float* __restrict__ y0, int n_tiles, int n,
@@ -194,8 +259,11 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     const f16x8* __restrict__ mimg, int n_in, float* __restrict__ v_out, int64_t ldvo,
     const WlScreen* __restrict__ scr, unsigned* __restrict__ scr_count, const int probe_on) {
   static_assert(!SCREEN || (NT == 1 && NKX == 0), "screening: one sample tile per wave, no mapper in front");
+  static_assert(!DRAIN || NKX == 0, "progress-ordered priority: the instances without a mapper");
   constexpr int NS = NKK * 2, NCH = NS * 2, NQ = NKK * 4, AUXR = WlGeom<NKK, (NKX > 0)>::AUXR;
   constexpr int NSX = NKX * 2, NQX = NKX * 4, MCH = NKK * NSX * 2;   // the mapper's K-steps, row pieces, 1-KiB chunks
+  constexpr bool SWAP = NKX == 0;      // (the mapped instances keep xhalf)
+  constexpr bool NANNV2 = SCREEN && RAYEN_WL_NANNV2 != 0;
   extern __shared__ __attribute__((aligned(1024))) char wl_smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -225,12 +293,14 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   bool stamp_on = false;
 #endif
 #ifdef RAYEN_WL_CLOCK
-  const bool probe = (blockIdx.x & 15) == 0 && threadIdx.x == 0;
-  if (probe) {
-    wl_clock_buf[(blockIdx.x >> 4) * 4 + 0] = __builtin_amdgcn_s_memtime();
-    wl_clock_buf[(blockIdx.x >> 4) * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-  }
+  const bool probe = (blockIdx.x & 15) == 0 && (blockIdx.x >> 4) < 16;      // (uniform: every wave of the workgroup stamps)
+  unsigned long long clock_at[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int clock_groups = 0;
+  RAYEN_WL_CLOCK_AT(0);
 #endif
+  // (DRAIN) the wave's progress level -- groups claimed so far, plus the steps inside its last group -- and the item at which
+  // the next step falls (never, outside a last group)
+  [[maybe_unused]] int drain_level = 0, drain_at = 0x7FFFFFFF;
 
   // ---- the image, once: chunk c (1 KiB) by wave c mod NW, by LDS-DMA (RAYEN_WL_HEAD; nothing passes through the registers, nothing
   // is waited for before the barrier).  See below the request lambda for the rest of the head.
@@ -410,6 +480,11 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     bool live[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) live[t] = (s_base + t * 32 + col) < B;
+    if constexpr (DRAIN) {
+      wl_set_level(drain_level);
+      drain_level = drain_level < 3 ? drain_level + 1 : 3;      // (the next group's level, or the first step inside this one)
+      drain_at = next >= n_groups ? n_items / 3 : 0x7FFFFFFF;
+    }
     if constexpr (!RAYEN_WL_AHEAD) {
       request(grp);
       half_max();
@@ -498,7 +573,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const float m = fmaxf(m_half[t], xhalf(m_half[t]));
+      const float m = wl_half_max<SWAP>(m_half[t]);
       float sv;
       int sv_exp;
       pow2_scale(m, sv, v_inv[t], sv_exp);
@@ -523,12 +598,12 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
           pair_split_hi(a, b, vraw[t][q][c + 1], sv);
           w1[j] = a;
           w2[j] = b;
-          pair_nan_fold(z, a);
+          if constexpr (!NANNV2) pair_nan_fold(z, a);
         }
         vb[t][0][sp] = __builtin_bit_cast(f16x8, w1);
         vb[t][1][sp] = __builtin_bit_cast(f16x8, w2);
       }
-      nan_row[t] = pair_nan_seen(z);
+      if constexpr (!NANNV2) nan_row[t] = pair_nan_seen(z);
     }
     // (SCREEN) ||sv v||^2 of the lane's row, from the SCALED values (a row of 1e-25 does not underflow to a bound of 0): two
     // chains over the lane's half, the halves added
@@ -543,8 +618,8 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
           s0 = fmaf(x0, x0, s0);
           s1 = fmaf(x1, x1, s1);
         }
-      nv2 = s0 + s1;
-      nv2 += xhalf(nv2);
+      nv2 = wl_half_sum<SWAP>(s0 + s1);
+      if constexpr (NANNV2) nan_row[0] = !(nv2 < __builtin_inff());
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- the next group's rows: in flight for the whole walk
@@ -589,6 +664,16 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
       const int n_walk = n_items - ((RAYEN_WL_ABL & 64) ? 4 : 0);
       for (int it = 0; it < n_walk; ++it) {
         RAYEN_WL_STAMP(it, 0);
+        if constexpr (DRAIN) {
+          if (it >= drain_at) {      // (a further step down inside the wave's last group)
+            wl_set_level(drain_level);
+            drain_level = drain_level < 3 ? drain_level + 1 : 3;
+            drain_at = drain_at < 2 * (n_items / 3) ? 2 * (n_items / 3) : 0x7FFFFFFF;
+          }
+        }
+#ifdef RAYEN_WL_CLOCK
+        if (it == 0 && clock_groups == 0) RAYEN_WL_CLOCK_AT(1);
+#endif
         const int ts = ts_next;      // (known since the previous item: nothing in front of the burst waits for a scalar load)
         // Two passes over the item's K-steps, by product size: the 2^-11 cross products first, the leading products last
         // (rayen_mfma_pair.hip).  A full tile multiplies all K-steps; the halves of a shared tile (rayen_tiles.h) K-steps
@@ -673,7 +758,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
           if (item.flags & MF_LAST) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-              const float total = part[t] + xhalf(part[t]);
+              const float total = wl_half_sum<SWAP>(part[t]);
               const float a0 = aux_lds[t][item.aux][col];
               float kc;
               if (item.type != MI_SOC) {
@@ -703,7 +788,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
               float qs = acc[t][4 * a] * acc[t][4 * a];
 #pragma unroll
               for (int c = 1; c < 4; ++c) qs = fmaf(acc[t][4 * a + c], acc[t][4 * a + c], qs);
-              if (pair) qs += xhalf(qs);
+              if (pair) qs = wl_half_sum<SWAP>(qs);
               const float kc = (aux_lds[t][slot & (AUXR - 1)][col] + __builtin_amdgcn_sqrtf(qs)) * (hi ? pk.inv[a][1] : pk.inv[a][0]);
               if (sid >= 0 && kc > kap[t]) { kap[t] = kc; acode[t] = sid << 20; }
             }
@@ -717,7 +802,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
             WlScreen s = sc_next;
             int nx = it + 1, ts_to = ts_next;
             int ts_held = ts_next;      // the item whose operands abuf holds in full (-2: a probe has overwritten leading pieces)
-            auto kmax_now = [&] { return fmaxf(kap[0], xhalf(kap[0])); };
+            auto kmax_now = [&] { return wl_half_max<SWAP>(kap[0]); };
             // (a NaN or an infinite row decides nothing: every comparison with it is false)
             const bool nv_ok = nv2 < __builtin_inff();
             // (the probe's margin is proved for a row whose largest scaled entry reached 2^13 -- every row but one below 2^-113,
@@ -773,7 +858,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
                   }
                   part[0] = s0 + s1;
                 }
-                const float total = part[0] + xhalf(part[0]);
+                const float total = wl_half_sum<SWAP>(part[0]);
                 const float r = __builtin_amdgcn_sqrtf(fmaxf(total, 0.f)) + __builtin_amdgcn_sqrtf(s.cabs * nv2);
                 const float tb = (r * r) * 1.000244140625f;      // (1 + 2^-12: the fp32 roundings of both sums and of this line)
                 const float a0 = aux_lds[0][s.aux][col];
@@ -812,12 +897,16 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     float knat[NT], scale[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const float other = xhalf(kap[t]);
-      if (TRACK) {
-        const int ocode = __shfl_xor(acode[t], 32);
-        if (other > kap[t] || (other == kap[t] && hi == 1)) acode[t] = ocode;
+      if (TRACK || !SWAP) {      // (the arg-max exchange needs the other half's value itself)
+        const float other = xhalf(kap[t]);
+        if (TRACK) {
+          const int ocode = __shfl_xor(acode[t], 32);
+          if (other > kap[t] || (other == kap[t] && hi == 1)) acode[t] = ocode;
+        }
+        kap[t] = fmaxf(kap[t], other);
+      } else {
+        kap[t] = wl_half_max<SWAP>(kap[t]);
       }
-      kap[t] = fmaxf(kap[t], other);
       knat[t] = (kap[t] * w_inv) * v_inv[t];
       scale[t] = v_inv[t] * (1.0f / fmaxf(1.0f, knat[t]));   // (the rebuilt direction carries sv only)
     }
@@ -868,6 +957,10 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
       bad |= live[t] && nan_row[t];      // (the row's own components: y is NaN exactly when one of them is NaN or Inf)
     }
     RAYEN_WL_STAMP(38, 2);
+#ifdef RAYEN_WL_CLOCK
+    if (clock_groups == 0) RAYEN_WL_CLOCK_AT(2);
+    ++clock_groups;
+#endif
     grp = next;
   }  // persistent loop over sample groups
   if (nan_flag && bad) atomicOr(nan_flag, 1);
@@ -875,9 +968,13 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     if (scr_count != nullptr && skipped != 0) atomicAdd(scr_count + lane, skipped);      // one atomic instruction per wave
   }
 #ifdef RAYEN_WL_CLOCK
-  if (probe) {
-    wl_clock_buf[(blockIdx.x >> 4) * 4 + 2] = __builtin_amdgcn_s_memtime();
-    wl_clock_buf[(blockIdx.x >> 4) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
+  RAYEN_WL_CLOCK_AT(3);
+  if (probe && lane == 0) {
+    unsigned long long* const rec = wl_clock_buf + ((blockIdx.x >> 4) * 16 + (wave & 15)) * kWlClockSlots;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rec[i] = clock_at[i];
+    rec[8] = __builtin_amdgcn_s_getreg(63492);      // (HW_REG_HW_ID, all 32 bits: the SIMD is bits 5:4)
+    rec[9] = (unsigned long long)clock_groups;
   }
 #endif
 }
@@ -1037,6 +1134,13 @@ int mfma_pair_wl_prepare(const RayenPack* p, PairImage* img) {
     want(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true>); want(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true>);
     want(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true>); want(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true>);
   }
+  // the instances of rayen_pair_drain(1)
+  want(mfma_pair_wl_kernel<1, false, kWlNT, kWlWaves, 0, false, true>); want(mfma_pair_wl_kernel<1, true, kWlNT, kWlWaves, 0, false, true>);
+  want(mfma_pair_wl_kernel<2, false, kWlNT, kWlWaves, 0, false, true>); want(mfma_pair_wl_kernel<2, true, kWlNT, kWlWaves, 0, false, true>);
+  if constexpr (kWlNT == 1) {
+    want(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true, true>); want(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true, true>);
+    want(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true, true>); want(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true, true>);
+  }
   if (!ok) return RAYEN_E_LAUNCH;
   img->wl_ready = true;
   // (RAYEN_PAIR_SCREEN_GATE=0 at pack creation: every qualifying segment stays decided -- tests and A/B runs)
@@ -1132,6 +1236,8 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
   const bool screen = kWlNT == 1 && img->wl_screen != nullptr && mode != 0;
   const int probe_on = mode == 1 ? 1 : 0;
   unsigned* const counters = wl_gate_counters != nullptr ? wl_gate_counters : pair_screen_counters_cell().load(std::memory_order_relaxed);
+  // (round 9: progress-ordered issue priority, rayen_pair_drain; the gate's launches run without it)
+  const bool drain_on = wl_gate_counters == nullptr && pair_drain_cell().load(std::memory_order_relaxed) != 0;
   // (round 8: this schedule's own order of the list, where pack creation found one)
   const MItem* const items = img->wl_items != nullptr ? img->wl_items : img->items;
   for (int64_t r0 = 0; r0 < B; r0 += rows_max) {
@@ -1150,25 +1256,30 @@ int mfma_pair_wl_forward(const RayenPack* p, const PairImage* img, const float* 
                          img->w_scale, img->w_inv, static_cast<const f16x8*>(nullptr), 0, static_cast<float*>(nullptr), (int64_t)0,
                          screen ? img->wl_screen : nullptr, screen ? counters : nullptr, probe_on);
     };
-    if constexpr (kWlNT == 1) {
-      if (screen) {
-        if (img->nkk == 1) {
-          if (active != nullptr) go(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true>);
-          else go(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true>);
-        } else {
-          if (active != nullptr) go(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true>);
-          else go(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true>);
+    auto pick = [&](auto drain) {      // (the same eight instances with and without progress-ordered priority)
+      constexpr bool D = decltype(drain)::value;
+      if constexpr (kWlNT == 1) {
+        if (screen) {
+          if (img->nkk == 1) {
+            if (active != nullptr) go(mfma_pair_wl_kernel<1, true, 1, kWlWaves, 0, true, D>);
+            else go(mfma_pair_wl_kernel<1, false, 1, kWlWaves, 0, true, D>);
+          } else {
+            if (active != nullptr) go(mfma_pair_wl_kernel<2, true, 1, kWlWaves, 0, true, D>);
+            else go(mfma_pair_wl_kernel<2, false, 1, kWlWaves, 0, true, D>);
+          }
+          return;
         }
-        continue;
       }
-    }
-    if (img->nkk == 1) {
-      if (active != nullptr) go(mfma_pair_wl_kernel<1, true, kWlNT, kWlWaves>);
-      else go(mfma_pair_wl_kernel<1, false, kWlNT, kWlWaves>);
-    } else {
-      if (active != nullptr) go(mfma_pair_wl_kernel<2, true, kWlNT, kWlWaves>);
-      else go(mfma_pair_wl_kernel<2, false, kWlNT, kWlWaves>);
-    }
+      if (img->nkk == 1) {
+        if (active != nullptr) go(mfma_pair_wl_kernel<1, true, kWlNT, kWlWaves, 0, false, D>);
+        else go(mfma_pair_wl_kernel<1, false, kWlNT, kWlWaves, 0, false, D>);
+      } else {
+        if (active != nullptr) go(mfma_pair_wl_kernel<2, true, kWlNT, kWlWaves, 0, false, D>);
+        else go(mfma_pair_wl_kernel<2, false, kWlNT, kWlWaves, 0, false, D>);
+      }
+    };
+    if (drain_on) pick(std::true_type{});
+    else pick(std::false_type{});
   }
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }

@@ -71,6 +71,10 @@ std::atomic<int>& pair_screen_cell();
 // the armed counter buffer (64 x uint32 on the device, slot = segment index) or null
 std::atomic<unsigned*>& pair_screen_counters_cell();
 
+// progress-ordered issue priority in the W-in-LDS schedule (round 9, "Drain" in rayen_mfma_pair_wl.hip): 0 off, 1 on
+// (RAYEN_PAIR_DRAIN at start-up, rayen_pair_drain afterwards)
+std::atomic<int>& pair_drain_cell();
+
 // eligibility is mfma_split_eligible's
 int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes);
 int mfma_pair_build_dense(const RayenPack* p, PairImage** out, int64_t* bytes);   // without shared tiles (fused mapper)

@@ -155,6 +155,20 @@ std::atomic<unsigned*>& pair_screen_counters_cell() {
   return buf;
 }
 
+std::atomic<int>& pair_drain_cell() {
+  static std::atomic<int> mode([] {
+    const char* e = std::getenv("RAYEN_PAIR_DRAIN");
+    return (e != nullptr && e[0] == '1') ? 1 : 0;
+  }());
+  return mode;
+}
+}  // namespace rayen
+extern "C" int rayen_pair_drain(int mode) {
+  if (mode == 0 || mode == 1) return rayen::pair_drain_cell().exchange(mode, std::memory_order_relaxed);
+  return rayen::pair_drain_cell().load(std::memory_order_relaxed);
+}
+namespace rayen {
+
 static int pair_build(const RayenPack* p, PairImage** out, int64_t* bytes, bool tri);
 int mfma_pair_build(const RayenPack* p, PairImage** out, int64_t* bytes) {
   // (RAYEN_PAIR_TRI=0: dense factors, two tiles each -- the image of rounds 3 and 4, for A/B measurements)

@@ -39,9 +39,16 @@ for B in [int(b) for b in args.batches.split(",")]:
         ops.project_raw(x, dp, want_active=False, want_kappa=False, out=y)
     e1.record()
     torch.cuda.synchronize()
-    buf = np.zeros(64, dtype=np.uint64)
-    assert fn(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
-    b = buf.reshape(16, 4).astype(np.float64)
+    if args.schedule == 3:
+        # (round 9: sixteen waves per probed workgroup, ten slots each -- [entry | first MFMA | end of first group | exit] x
+        # [s_memtime, s_memrealtime], HW_ID, groups walked; scripts/ubench/wl_drain.py reads all of it, this script wave 0)
+        buf = np.zeros(16 * 16 * 10, dtype=np.uint64)
+        assert fn(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
+        b = buf.reshape(16, 16, 10)[:, 0, [0, 1, 6, 7]].astype(np.float64)
+    else:
+        buf = np.zeros(64, dtype=np.uint64)
+        assert fn(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
+        b = buf.reshape(16, 4).astype(np.float64)
     b = b[b[:, 3] > b[:, 1]]        # (probes of workgroups that ran)
     ticks, real = b[:, 2] - b[:, 0], (b[:, 3] - b[:, 1]) / 100e6
     ghz = ticks / real / 1e9
