@@ -567,6 +567,9 @@ int rayen_soft_cost_f64(const RayenCostPack* pack, const double* y, int64_t B, i
 /* ---- The soft cost in fp64 on the fp64 matrix cores, opt-in (additive to ABI v15) */
 #include "rayen_hip_cost_tile64.h"
 
+/* ---- The mapper v = Wm x + b in front of the fp64 matrix-core forward, one launch (additive to ABI v15) */
+#include "rayen_hip_mapped64.h"
+
 #ifdef __cplusplus
 }
 #endif

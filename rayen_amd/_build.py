@@ -64,7 +64,7 @@ def is_stale():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
     deps += [os.path.join(INCLUDE, f) for f in ("rayen_hip.h", "rayen_hip_tile.h", "rayen_hip_tile64.h", "rayen_hip_dc3_tile.h", "rayen_hip_dc3_tile64.h", "rayen_hip_cost_stream.h",
                                                 "rayen_hip_bar_stream.h", "rayen_hip_wide_fused.h", "rayen_hip_wide_fused_bwd.h",
-                                                "rayen_hip_wide_fused64.h", "rayen_hip_wide_fused_bwd64.h", "rayen_hip_cost_tile64.h")]
+                                                "rayen_hip_wide_fused64.h", "rayen_hip_wide_fused_bwd64.h", "rayen_hip_cost_tile64.h", "rayen_hip_mapped64.h")]
     return any(os.path.getmtime(d) > built for d in deps)
 
 

@@ -80,6 +80,9 @@ EXPORTS_WIDE_FUSED_BWD64 = ("rayen_wide_fused_bwd64_served", "rayen_wide_fused_b
 # additive to ABI v15, declared in include/rayen_hip_cost_tile64.h (which rayen_hip.h includes, like the eight above);
 # tests/test_cost_tile64_host.py holds the two against each other
 EXPORTS_COST_TILE64 = ("rayen_cost_tile64_set", "rayen_cost_tile64_served", "rayen_soft_cost_tile64_f64")
+# additive to ABI v15, declared in include/rayen_hip_mapped64.h (which rayen_hip.h includes, like the nine above);
+# tests/test_mapped64_host.py holds the two against each other
+EXPORTS_MAPPED64 = ("rayen_mapper_fusable_f64", "rayen_ray_project_mapped_f64")
 KERNEL_NONE, KERNEL_LANE, KERNEL_MFMA, KERNEL_TRIPLE, KERNEL_PAIR, KERNEL_PAIR_IO, KERNEL_LMI_QUAD, KERNEL_LMI_WAVE, KERNEL_PAIR_WS, KERNEL_PRODUCTS, KERNEL_LMI_BLOCK, KERNEL_PAIR_WL = range(12)
 KERNEL_WIDE_FUSED = 12
 KERNEL_WIDE_FUSED64 = 13
@@ -209,6 +212,11 @@ def load():
     lib.rayen_mapper_fusable.argtypes = [p, ctypes.c_int32]
     lib.rayen_ray_project_mapped_f32.restype = ctypes.c_int
     lib.rayen_ray_project_mapped_f32.argtypes = [p, p, i64, i64, ctypes.c_int32, p, i64, p, p, i64, p, i64,
+                                                 p, i32p, i32p, p]
+    lib.rayen_mapper_fusable_f64.restype = ctypes.c_int
+    lib.rayen_mapper_fusable_f64.argtypes = [p, ctypes.c_int32]
+    lib.rayen_ray_project_mapped_f64.restype = ctypes.c_int
+    lib.rayen_ray_project_mapped_f64.argtypes = [p, p, i64, i64, ctypes.c_int32, p, i64, p, p, i64, p, i64,
                                                  p, i32p, i32p, p]
     for name in ("rayen_bwd_workspace_bytes_f32", "rayen_bwd_workspace_bytes_f64"):
         getattr(lib, name).restype = ctypes.c_int64

@@ -90,10 +90,17 @@ class ConstraintModule(torch.nn.Module):
     WIDE_BACKWARDS = ops.WIDE_BACKWARDS
 
     def __init__(self, cs, input_dim=None, method='RAYEN', create_map=True, args_DC3=None, *, bar_kernel='resident',
-                 bar_window_bytes=0, wide_kernel='products', wide_backward='products'):
+                 bar_window_bytes=0, wide_kernel='products', wide_backward='products', fuse_mapper64=False):
         super().__init__()
 
         self.method = method
+        if fuse_mapper64 and method != 'RAYEN':
+            raise ValueError(f"fuse_mapper64={fuse_mapper64!r} chooses a kernel of method 'RAYEN'; this module's method is {method!r}")
+        # fp64 input behind an nn.Linear mapper: True evaluates the mapper inside the fp64 matrix-core forward (the MAPPED
+        # instances of rayen_mfma_f64.hip: one launch, v written only for the backward) where ops.mapper_fusable64 serves
+        # the call, and runs the two ops otherwise, silently, as fuse_mapper does in fp32.  Off by default: no timing
+        # enters a dispatch here.  fuse_mapper = False switches both precisions off.
+        self.fuse_mapper64 = bool(fuse_mapper64)
         if wide_kernel not in self.WIDE_KERNELS:
             raise ValueError(f"wide_kernel must be one of {self.WIDE_KERNELS}, got {wide_kernel!r}")
         if wide_kernel != 'products' and method != 'RAYEN':
@@ -320,6 +327,7 @@ class ConstraintModule(torch.nn.Module):
         self.__dict__.setdefault("bar_window_bytes", 0)
         self.__dict__.setdefault("wide_kernel", 'products')      # (pickles from before the fused wide forward)
         self.__dict__.setdefault("wide_backward", 'products')    # (pickles from before the fused wide backward)
+        self.__dict__.setdefault("fuse_mapper64", False)         # (pickles from before the fused fp64 mapper)
         self.forwardForMethod = {'RAYEN': self.forwardForRAYEN, 'RAYEN_old': self.forwardForRAYENOld,
                                  'UU': self.forwardForUU, 'Bar': self.forwardForBar,
                                  'DC3': self.forwardForDC3}[self.method]
@@ -563,10 +571,13 @@ class ConstraintModule(torch.nn.Module):
         return self.NA_E.T @ (y - self.yp)
 
     def _forward_fused_mapper(self, x2):
-        """mapper + projection as ONE kernel launch (``rayen_amd::ray_project_mapped``) or ``None`` when
+        """mapper + projection as ONE kernel launch (``rayen_amd::ray_project_mapped``; fp64 input with
+        ``fuse_mapper64``: ``rayen_amd::ray_project_mapped64``) or ``None`` when
         the fused kernel does not serve this layer/input (then the two-op path below runs)."""
         if (self.method != 'RAYEN' or not getattr(self, "fuse_mapper", True)
-                or not isinstance(self.mapper, nn.Linear) or not x2.is_cuda or x2.dtype != torch.float32
+                or not isinstance(self.mapper, nn.Linear) or not x2.is_cuda
+                or x2.dtype not in (torch.float32, torch.float64)
+                or (x2.dtype == torch.float64 and not getattr(self, "fuse_mapper64", False))
                 or self._refused(x2)):
             return None
         try:
@@ -574,11 +585,13 @@ class ConstraintModule(torch.nn.Module):
         except _lib.RayenError:
             return None           # (the two-op path below reports it)
         weight, bias = self.mapper.weight, self.mapper.bias
-        if not ops.mapper_fusable(x2, weight, bias, dp):
+        f64 = x2.dtype == torch.float64
+        if not (ops.mapper_fusable64 if f64 else ops.mapper_fusable)(x2, weight, bias, dp):
             return None
         need_grad = torch.is_grad_enabled() and (x2.requires_grad or weight.requires_grad
                                                  or (bias is not None and bias.requires_grad))
-        y, _, _, _ = torch.ops.rayen_amd.ray_project_mapped(x2, weight, bias, pack_id, need_grad)
+        op = torch.ops.rayen_amd.ray_project_mapped64 if f64 else torch.ops.rayen_amd.ray_project_mapped
+        y, _, _, _ = op(x2, weight, bias, pack_id, need_grad)
         return y.unsqueeze(2)
 
     # ------------------------------------------------------------------ small-batch inference fast path

@@ -1113,6 +1113,26 @@ int rayen_ray_project_f64(const RayenPack* p, const double* v, int64_t B, int64_
   return project_f64(p, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, 0);
 }
 
+int rayen_mapper_fusable_f64(const RayenPack* p, int32_t in_dim) {
+  if (p == nullptr || check_ready<double>(p, false) != RAYEN_OK) return 0;
+  return mfma64_mapper_fusable(p, p->m64, in_dim) ? 1 : 0;
+}
+
+int rayen_ray_project_mapped_f64(const RayenPack* p, const double* x, int64_t B, int64_t ldx, int32_t in_dim,
+                                 const double* Wm, int64_t ldw, const double* bias, double* v_out, int64_t ldvo,
+                                 double* y, int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag,
+                                 void* stream) {
+  if (p == nullptr || B < 0 || in_dim <= 0 || ldx < in_dim || ldw < in_dim || Wm == nullptr || y == nullptr ||
+      ldy < p->k || (B > 0 && x == nullptr) || (v_out != nullptr && ldvo < p->n))
+    return RAYEN_E_BAD_ARG;
+  const int rc = check_ready<double>(p, false);
+  if (rc) return rc;
+  if (p->m64 == nullptr) return RAYEN_E_UNSUPPORTED;
+  g_last_forward = RAYEN_KERNEL_MFMA;
+  return mfma64_forward_mapped(p, p->m64, x, B, ldx, in_dim, Wm, ldw, bias, v_out, ldvo, y, ldy, kappa, active,
+                               nan_flag, static_cast<hipStream_t>(stream));
+}
+
 int rayen_ray_project_old_f64(const RayenPack* p, const double* v, int64_t B, int64_t ldv, double* y,
                               int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag, void* stream) {
   return project_f64(p, v, B, ldv, y, ldy, kappa, active, nan_flag, stream, 1);

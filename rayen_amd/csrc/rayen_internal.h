@@ -423,4 +423,11 @@ int mfma64_forward(const RayenPack* p, const Mfma64Image* img, const double* v, 
                    double* y, int64_t ldy, double* kappa, int32_t* active, int32_t* nan_flag,
                    int old_mode, hipStream_t stream);
 
+// ... with the mapper v = Wm x + b fused in front (its MAPPED instances)
+bool mfma64_mapper_fusable(const RayenPack* p, const Mfma64Image* img, int in_dim);
+int mfma64_forward_mapped(const RayenPack* p, const Mfma64Image* img, const double* x, int64_t B, int64_t ldx,
+                          int in_dim, const double* w, int64_t ldw, const double* bias, double* v_out,
+                          int64_t ldvo, double* y, int64_t ldy, double* kappa, int32_t* active,
+                          int32_t* nan_flag, hipStream_t stream);
+
 }  // namespace rayen

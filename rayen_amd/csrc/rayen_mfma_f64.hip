@@ -34,18 +34,30 @@ struct Mfma64Image {
 };
 
 constexpr int k64Waves = 8;
+constexpr int k64MapMaxIn = 512;  // widest fused mapper (a runtime loop over 32-column blocks of x: not a register limit)
+
+// The module's mapper v = Wm x + b in front of the walk (MAPPED instances): weights read in place from
+// nn.Linear.weight (row-major [n, ldw]), x takes the place of v in the kernel's arguments.
+struct Mapper64Args {
+  const double* w = nullptr;
+  int64_t ldw = 0;
+  const double* bias = nullptr;  // NULL: no bias
+  int in_dim = 0;
+  double* v_out = nullptr;       // NULL: v stays in registers
+  int64_t ldvo = 0;
+};
 
 template <typename T>
 __device__ __forceinline__ T xq16(T x) { return __shfl_xor(x, 16); }
 template <typename T>
 __device__ __forceinline__ T xq32(T x) { return __shfl_xor(x, 32); }
 
-template <int NKK, bool TRACK>
+template <int NKK, bool TRACK, bool MAPPED = false>
 __global__ __launch_bounds__(k64Waves * 64, 2) void mfma64_fwd_kernel(
     const f64x2* __restrict__ Wimg, const MItem* __restrict__ items, int n_items,
     const MPack* __restrict__ packs, const double* __restrict__ y0, int identity, int k, int n, const double* __restrict__ v, int64_t B,
     int64_t ldv, double* __restrict__ y, int64_t ldy, double* __restrict__ kappa_out,
-    int32_t* __restrict__ active_out, int32_t* __restrict__ nan_flag, int old_mode) {
+    int32_t* __restrict__ active_out, int32_t* __restrict__ nan_flag, int old_mode, Mapper64Args mp) {
   constexpr int NS = NKK * 8;   // K-steps (4 columns each) per tile
   __shared__ double aux_lds[k64Waves][2][32][16];  // [wave][column block][aux row][sample]
 
@@ -64,6 +76,7 @@ __global__ __launch_bounds__(k64Waves * 64, 2) void mfma64_fwd_kernel(
     // ---- B operands: element 4s + q of each of this lane's two samples
     double vb[2][NS];
     bool live[2];
+    if constexpr (!MAPPED) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const int64_t s = s_base + 16 * c + j;
@@ -72,10 +85,90 @@ __global__ __launch_bounds__(k64Waves * 64, 2) void mfma64_fwd_kernel(
 #pragma unroll
       for (int st = 0; st < NS; ++st) vb[c][st] = (live[c] && 4 * st + q < n) ? row[4 * st + q] : 0.0;
     }
+    } else {
+      // mapper: v = bias + Wm x on the matrix cores.  Result register g of row half rh of tile tp holds row
+      // 32 tp + 16 rh + 4 g + q = element 4 (8 tp + 4 rh + g) + q of v: the accumulators ARE vb[c][8 tp + 4 rh + g].
+      // x (in the place of v) is walked in blocks of 32 columns = eight K-steps, one block live at a time; the A
+      // operands are 8-byte loads of the lane's weight row, zero beyond n rows / in_dim columns.
+      const double* xrow[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int64_t s = s_base + 16 * c + j;
+        live[c] = s < B;
+        xrow[c] = v + (live[c] ? s : 0) * ldv;
+      }
+      f64x4 macc[NKK][2][2];  // [tile][row half][column block]
+#pragma unroll
+      for (int tp = 0; tp < NKK; ++tp)
+#pragma unroll
+        for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int r = 32 * tp + 16 * rh + 4 * g + q;
+            const double b = (mp.bias != nullptr && r < n) ? mp.bias[r] : 0.0;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) macc[tp][rh][c][g] = live[c] ? b : 0.0;
+          }
+      // (the next block of x is requested before this block's MFMAs: its trip to memory hides behind them)
+      double xb[2][8], xn[2][8];
+      auto fetch_x = [&](double (&buf)[2][8], const int col) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int st = 0; st < 8; ++st) buf[c][st] = (live[c] && col + 4 * st < mp.in_dim) ? xrow[c][col + 4 * st] : 0.0;
+      };
+      fetch_x(xb, q);
+      for (int c0 = 0; c0 < mp.in_dim; c0 += 32) {
+        const int col = c0 + q;  // + 4 st
+        double wa[NKK][2][8];
+#pragma unroll
+        for (int tp = 0; tp < NKK; ++tp)
+#pragma unroll
+          for (int rh = 0; rh < 2; ++rh) {
+            const int wr = 32 * tp + 16 * rh + j;
+            const double* wrow = mp.w + (int64_t)(wr < n ? wr : 0) * mp.ldw;
+#pragma unroll
+            for (int st = 0; st < 8; ++st) wa[tp][rh][st] = (wr < n && col + 4 * st < mp.in_dim) ? wrow[col + 4 * st] : 0.0;
+          }
+        fetch_x(xn, col + 32);  // (all zero past the last block: predicated off)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int st = 0; st < 8; ++st)
+#pragma unroll
+          for (int tp = 0; tp < NKK; ++tp)
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+              for (int c = 0; c < 2; ++c)
+                macc[tp][rh][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[tp][rh][st], xb[c][st], macc[tp][rh][c], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int st = 0; st < 8; ++st) xb[c][st] = xn[c][st];
+      }
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int tp = 0; tp < NKK; ++tp)
+#pragma unroll
+          for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) vb[c][8 * tp + 4 * rh + g] = macc[tp][rh][c][g];
+      if (mp.v_out != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          if (!live[c]) continue;
+          double* vrow = mp.v_out + (s_base + 16 * c + j) * mp.ldvo;
+#pragma unroll
+          for (int st = 0; st < NS; ++st)
+            if (4 * st + q < n) vrow[4 * st + q] = vb[c][st];
+        }
+      }
+    }
 
     // RAYEN_old head (rayen/constraint_module.py:460-466): y = y0 + N v / (||v|| e^beta + kappa(v))
     double old_den[2] = {0.0, 0.0};
-    if (old_mode) {
+    if (!MAPPED && old_mode) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         double nrm2 = 0.0;
@@ -436,11 +529,30 @@ static int launch64(const RayenPack* p, const Mfma64Image* img, const double* v,
   if (active != nullptr) {
     hipLaunchKernelGGL((mfma64_fwd_kernel<NKK, true>), dim3((unsigned)grid), dim3(k64Waves * 64), 0, stream,
                        img->W, img->items, img->n_items, img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, y, ldy,
-                       kappa, active, nan_flag, old_mode);
+                       kappa, active, nan_flag, old_mode, Mapper64Args());
   } else {
     hipLaunchKernelGGL((mfma64_fwd_kernel<NKK, false>), dim3((unsigned)grid), dim3(k64Waves * 64), 0, stream,
                        img->W, img->items, img->n_items, img->packs, img->y0, img->identity, p->k, p->n, v, B, ldv, y, ldy,
-                       kappa, active, nan_flag, old_mode);
+                       kappa, active, nan_flag, old_mode, Mapper64Args());
+  }
+  return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
+}
+
+template <int NKK>
+static int launch64_mapped(const RayenPack* p, const Mfma64Image* img, const double* x, int64_t B, int64_t ldx,
+                           const Mapper64Args& mp, double* y, int64_t ldy, double* kappa, int32_t* active,
+                           int32_t* nan_flag, hipStream_t stream) {
+  const int64_t n_groups = (B + 31) / 32;
+  const int64_t slots = (int64_t)launch_simds(img->n_simd) * 2;
+  const int64_t grid = grid_for_groups(n_groups, slots, k64Waves);
+  if (active != nullptr) {
+    hipLaunchKernelGGL((mfma64_fwd_kernel<NKK, true, true>), dim3((unsigned)grid), dim3(k64Waves * 64), 0, stream,
+                       img->W, img->items, img->n_items, img->packs, img->y0, img->identity, p->k, p->n, x, B, ldx, y, ldy,
+                       kappa, active, nan_flag, 0, mp);
+  } else {
+    hipLaunchKernelGGL((mfma64_fwd_kernel<NKK, false, true>), dim3((unsigned)grid), dim3(k64Waves * 64), 0, stream,
+                       img->W, img->items, img->n_items, img->packs, img->y0, img->identity, p->k, p->n, x, B, ldx, y, ldy,
+                       kappa, active, nan_flag, 0, mp);
   }
   return hipGetLastError() == hipSuccess ? RAYEN_OK : RAYEN_E_LAUNCH;
 }
@@ -452,6 +564,29 @@ int mfma64_forward(const RayenPack* p, const Mfma64Image* img, const double* v, 
   if (img->nkk == 1) return launch64<1>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, old_mode, stream);
   if (img->nkk == 2) return launch64<2>(p, img, v, B, ldv, y, ldy, kappa, active, nan_flag, old_mode, stream);
   return RAYEN_E_UNSUPPORTED;
+}
+
+// the same walk behind the module's mapper: every load of x and Wm is one double, so any ldx, ldw >= in_dim is served
+bool mfma64_mapper_fusable(const RayenPack* p, const Mfma64Image* img, int in_dim) {
+  (void)p;
+  return img != nullptr && (img->nkk == 1 || img->nkk == 2) && in_dim >= 1 && in_dim <= k64MapMaxIn;
+}
+
+int mfma64_forward_mapped(const RayenPack* p, const Mfma64Image* img, const double* x, int64_t B, int64_t ldx,
+                          int in_dim, const double* w, int64_t ldw, const double* bias, double* v_out,
+                          int64_t ldvo, double* y, int64_t ldy, double* kappa, int32_t* active,
+                          int32_t* nan_flag, hipStream_t stream) {
+  if (!mfma64_mapper_fusable(p, img, in_dim)) return RAYEN_E_UNSUPPORTED;
+  if (B == 0) return RAYEN_OK;
+  Mapper64Args mp;
+  mp.w = w;
+  mp.ldw = ldw;
+  mp.bias = bias;
+  mp.in_dim = in_dim;
+  mp.v_out = v_out;
+  mp.ldvo = ldvo;
+  if (img->nkk == 1) return launch64_mapped<1>(p, img, x, B, ldx, mp, y, ldy, kappa, active, nan_flag, stream);
+  return launch64_mapped<2>(p, img, x, B, ldx, mp, y, ldy, kappa, active, nan_flag, stream);
 }
 
 }  // namespace rayen

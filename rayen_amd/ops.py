@@ -604,6 +604,72 @@ def _mapped_backward(ctx, grad_y, grad_kappa, grad_active, grad_v_out):
 ray_project_mapped.register_autograd(_mapped_backward, setup_context=_mapped_setup_context)
 
 
+# ... and in fp64: the mapper in front of the fp64 matrix-core forward (include/rayen_hip_mapped64.h), weights read in place
+
+def mapper_fusable64(x, weight, bias, pack):
+    """Can ``ray_project_mapped64`` serve this call?  (fp64 device tensors, ``weight [n, in_dim]`` with unit column stride
+    -- any row stride: every load is one double --, and a pack the fp64 matrix-core forward serves, ``in_dim <= 512``.)"""
+    if not (x.is_cuda and weight.is_cuda and x.dtype == torch.float64 and weight.dtype == torch.float64 and x.dim() == 2
+            and weight.dim() == 2 and weight.shape[0] == pack.consts.n and x.shape[1] == weight.shape[1]
+            and weight.shape[1] >= 1 and weight.stride(1) == 1 and weight.stride(0) >= weight.shape[1]
+            and (bias is None or (bias.is_cuda and bias.dtype == torch.float64 and bias.is_contiguous()
+                                  and bias.shape == (pack.consts.n,)))):
+        return False
+    return pack.mapper_mode64(weight.shape[1]) == 1
+
+
+@torch.library.custom_op("rayen_amd::ray_project_mapped64", mutates_args=())
+def ray_project_mapped64(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], pack_id: int,
+                         need_grad: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(y, kappa, active, v)`` of ``ray_project_mapped`` in fp64: ``v = x weight' + bias`` formed on the fp64 matrix
+    cores inside the projection kernel.
+
+    ``need_grad``: also write ``v`` and the active-constraint record (the backward's inputs); without it
+    ``v`` never reaches memory and both come back empty."""
+    pack = _pack(pack_id)
+    if not mapper_fusable64(x, weight, bias, pack):
+        raise RuntimeError("rayen_amd::ray_project_mapped64: unsupported mapper (check ops.mapper_fusable64 first)")
+    if x.device.index != pack.device_index:
+        raise RuntimeError("rayen_amd: input and constant pack live on different devices")
+    B, in_dim = x.shape
+    if x.stride(1) != 1 or (B > 1 and x.stride(0) < in_dim):
+        x = x.contiguous()
+    k, n = pack.consts.k, pack.consts.n
+    y = torch.empty((B, k), dtype=x.dtype, device=x.device)
+    kappa = torch.empty((B,), dtype=x.dtype, device=x.device)
+    active = torch.empty((B if need_grad else 0, 2), dtype=torch.int32, device=x.device)
+    v = torch.empty((B if need_grad else 0, n), dtype=x.dtype, device=x.device)
+    if B == 0:
+        return y, kappa, active, v           # (empty tensors have no address to hand to the library)
+    with _on_device(x.device):
+        code = _lib.load().rayen_ray_project_mapped_f64(
+            pack.handle, _ptr(x), B, x.stride(0) if B > 1 else in_dim, in_dim, _ptr(weight), weight.stride(0),
+            _ptr(bias), _ptr(v) if need_grad else None, n, _ptr(y), k, _ptr(kappa),
+            _ptr(active) if need_grad else None, _ptr(pack.nan_flag), _stream(x.device.index))
+    _lib.check(code, "rayen_ray_project_mapped64")
+    return y, kappa, active, v
+
+
+@ray_project_mapped64.register_fake
+def _(x, weight, bias, pack_id, need_grad):
+    pack = _pack(pack_id)
+    B = x.shape[0]
+    rows = B if need_grad else 0
+    return (x.new_empty((B, pack.consts.k)), x.new_empty((B,)),
+            x.new_empty((rows, 2), dtype=torch.int32), x.new_empty((rows, pack.consts.n)))
+
+
+def _mapped64_setup_context(ctx, inputs, output):
+    if not inputs[4]:
+        raise RuntimeError("rayen_amd::ray_project_mapped64 was called with need_grad=False on inputs that "
+                           "require grad")
+    _mapped_setup_context(ctx, inputs, output)
+
+
+# (the same formula: d y / d v on the HIP backward kernel from the saved v, the three mapper products in torch)
+ray_project_mapped64.register_autograd(_mapped_backward, setup_context=_mapped64_setup_context)
+
+
 # ------------------------------------------------------------------------------------------------
 # What the side layers below (Bar, DC3, Euclidean projection, soft cost) share: each owns an opaque pack of the library
 # (rayen_<layer>_pack_create / _destroy: an fp32 and an fp64 image on one device), tests its input rows the same way and

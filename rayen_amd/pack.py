@@ -293,6 +293,16 @@ class DevicePack:
                 cache[in_dim] = int(_lib.load().rayen_mapper_fusable(self.handle, int(in_dim)))
         return cache[in_dim]
 
+    def mapper_mode64(self, in_dim):
+        """``rayen_mapper_fusable_f64``: 1 = the fp64 matrix-core forward takes an ``in_dim``-wide mapper in front (weights
+        read in place) | 0 = no fused form in fp64."""
+        import torch
+        cache = self.__dict__.setdefault("_fusable64", {})   # (the answer is fixed at pack creation)
+        if in_dim not in cache:
+            with torch.cuda.device(self.device_index):
+                cache[in_dim] = int(_lib.load().rayen_mapper_fusable_f64(self.handle, int(in_dim)))
+        return cache[in_dim]
+
     def mapper_fusable(self, in_dim):
         """True when one of the fused mapper + projection entry points serves an ``in_dim``-wide mapper."""
         return self.mapper_mode(in_dim) != 0
