@@ -11,11 +11,15 @@
 // buys besides:
 //   * no row buffers in LDS (there is no room for them and no need): a lane reads ITS sample's row straight from memory as
 //     eight 16-byte pieces (fragment shape: lanes (col, hi) of a row cover 32 contiguous bytes, four consecutive
-//     instructions complete a 128-byte line) at the top of its group -- the wait is left to the other waves of the SIMD --
+//     instructions complete a 128-byte line) -- the wait is left to the other waves of the SIMD; requested at the top of the
+//     group in rounds 6-9 and in the mapped instances; since round 10 (RAYEN_WL_HEAD bit 2) the first group's in the head --
+//     two waves of the workgroup behind the image's chunks in front of the barrier, the others right behind it -- and every
+//     further group's behind the last store of y of the group before --
 //     through a buffer descriptor whose extent is the batch (one add per group; rows beyond the batch and pieces beyond
 //     a ragged width are out of range: loads return 0, stores are dropped), and writes its row of y through 2 KiB of LDS
 //     as whole lines;
-//   * vmcnt counts nothing but those rows: no counted waits, no stand-in operations;
+//   * vmcnt counts nothing but those rows and the stores of y: one counted wait, in the head of the early waves (the image has
+//     landed, the first rows are in flight), no stand-in operations;
 //   * groups of 32 samples (one sample tile per wave): ~120 instead of 160+ live registers, so FOUR waves per SIMD
 //     (sixteen per workgroup, dealt groups on demand from a counter in LDS) take turns on the matrix pipe -- by the same
 //     microbenchmark a partner's plain VALU / SALU / LDS instructions issue while a wave's MFMAs execute; measured
@@ -112,9 +116,28 @@ constexpr int kWlNT = RAYEN_WL_NT;            // sample tiles (of 32) per wave a
 #endif
 // bit 0: the image is copied by LDS-DMA (0: through registers) | bit 1: a wave's first rows are pulled towards L2 meanwhile
 // (config 3, B = 262 144, gpurun_out/r06zza: 0 -> 46.1-46.6 us, 1 -> 45.3-45.9, 2 -> 47.4-49.4: the extra requests cost more than the
-// round trip they hide)
+// round trip they hide) | bit 2 (round 10; the instances without a mapper, RAYEN_WL_AHEAD = 0): the first rows of the workgroup's
+// first RAYEN_WL_EARLY waves are REQUESTED behind the image's chunks and in front of the barrier -- into their registers, once; the
+// wait in front of the barrier is for the image alone (vmcnt retires in order: the rows stay in flight) -- those of the other
+// waves right behind the barrier, and a further group's rows at the bottom of the group in front of it, behind its last store of
+// y.  -DRAYEN_WL_HEAD=1 (scripts/ubench/tu_variant.sh) rebuilds the head of rounds 6-9 for a same-box A/B.
 #ifndef RAYEN_WL_HEAD
-#define RAYEN_WL_HEAD 1
+#define RAYEN_WL_HEAD 5
+#endif
+// (RAYEN_WL_HEAD bit 2) how many waves of a workgroup request their first rows in front of the barrier.  The image and the rows
+// come through the same vector-memory path of the CU, so rows requested early do not arrive sooner in all, they only arrive
+// before the barrier opens: with all sixteen early the four waves of a SIMD left the barrier into their splits together and
+// the launch was SLOWER at every batch size (config 3, five interleaved runs each, against the head of rounds 6-9: B = 262 144
+// 0.03927-0.03963 against 0.03875-0.03899 ms, 32 768 +1.5 %, 1 048 576 +0.5 %; entry to first MFMA 6.4-6.8 against 5.7-5.8 us).
+// With two early those two multiply while the others' rows arrive and are split: 0.04000-0.04033 against 0.04021-0.04092
+// (parent 0.04060-0.04088), 32 768 0.01318-0.01328 against 0.01333-0.01348; four: no gain at 262 144, a loss at 32 768 (all of
+// its busy waves early); eight: the parent's time (profiles/bench/r10_wl_head_probe.txt).
+#ifndef RAYEN_WL_EARLY
+#define RAYEN_WL_EARLY 2
+#endif
+// 1: the running maximum over both halves is formed once per decision point (round 10) | 0: once per test, as in rounds 7-9
+#ifndef RAYEN_WL_KMAX_ONCE
+#define RAYEN_WL_KMAX_ONCE 1
 #endif
 // aux rows a wave keeps per sample tile: 32 at NKK = 1; at NKK = 2 sixteen (2 KiB: what the staging of y needs anyway), eight in the
 // mapped instances (1 KiB: the mapper's image takes the room)
@@ -264,6 +287,9 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   constexpr int NSX = NKX * 2, NQX = NKX * 4, MCH = NKK * NSX * 2;   // the mapper's K-steps, row pieces, 1-KiB chunks
   constexpr bool SWAP = NKX == 0;      // (the mapped instances keep xhalf)
   constexpr bool NANNV2 = SCREEN && RAYEN_WL_NANNV2 != 0;
+  // (RAYEN_WL_HEAD bit 2) the first rows requested in the head, the next ones at the bottom of a group.  The mapped instances keep
+  // the request at the top of the group: they sit at 128 registers with spills already, and their rows feed the mapper first
+  constexpr bool ROWS_FIRST = (RAYEN_WL_HEAD & 4) != 0 && (RAYEN_WL_HEAD & 2) == 0 && NKX == 0 && RAYEN_WL_AHEAD == 0;
   extern __shared__ __attribute__((aligned(1024))) char wl_smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -302,8 +328,8 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   // the next step falls (never, outside a last group)
   [[maybe_unused]] int drain_level = 0, drain_at = 0x7FFFFFFF;
 
-  // ---- the image, once: chunk c (1 KiB) by wave c mod NW, by LDS-DMA (RAYEN_WL_HEAD; nothing passes through the registers, nothing
-  // is waited for before the barrier).  See below the request lambda for the rest of the head.
+  // ---- the image, once: chunk c (1 KiB) by wave c mod NW, by LDS-DMA (RAYEN_WL_HEAD; nothing passes through the registers).  See
+  // below the request lambda for the rest of the head: the early waves' first rows behind the chunks, a wait for the chunks alone.
   for (int i = threadIdx.x; i < NKK * 32; i += NW * 64) y0_lds[i] = y0[i];
   if (threadIdx.x == 0) *take_lds = NW;     // (the first NW are the waves' first groups)
   float gm_inv = 1.f;
@@ -343,7 +369,10 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   const bool ragged_n = n < NKK * 32;
   const bool ragged_in = NKX > 0 && n_in < NKX * 32;
   constexpr unsigned kNowhere = 0xFFFFFFF0u;
-  auto request = [&](const int64_t g) {
+  // (`one_copy`: the head's request, once per wave -- a select per piece instead of the two copies, so that exactly NT * NQ loads
+  // stand between the image's chunks and the counted wait)
+  auto request = [&](const int64_t g, auto one_copy) {
+    constexpr bool ONE = decltype(one_copy)::value;
     const unsigned goff = v_lane_off + (unsigned)g * (unsigned)(NT * 32) * (unsigned)ldv * 4u;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -365,7 +394,14 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
       } else {
         // (two copies behind a wave-uniform branch, the empty statement keeps hipcc from folding them back into one with a select
         // per piece: at the padded width -- the headline -- the selects were 3 % of the kernel's vector instructions)
-        if (__builtin_expect(ragged_n, 0)) {
+        if constexpr (ONE) {
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) {
+            unsigned off = goff + (unsigned)t * 32u * (unsigned)ldv * 4u + 32u * q;
+            off = (8 * q + 4 * hi < n) ? off : kNowhere;
+            vraw[t][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, off, 0, 0));
+          }
+        } else if (__builtin_expect(ragged_n, 0)) {
           asm volatile("; ragged width" ::: "memory");
 #pragma unroll
           for (int q = 0; q < NQ; ++q) {
@@ -441,9 +477,10 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
   };
 #if RAYEN_WL_HEAD
   {
-    // the image's chunks, then -- behind them, loads retire in order -- the wave's first rows, pulled towards L2 into the wave's own
-    // (still unused) kilobyte and thrown away: the group's real request at the top of the walk finds the lines in L2 instead of
-    // paying an HBM round trip behind the barrier.  Whole groups only (this path has no bounds).  Only the image is waited for.
+    // the image's chunks, then -- behind them, loads retire in order -- the wave's first rows.  Bit 2 (ROWS_FIRST): the group's real
+    // request, into the row registers; the HBM round trip runs while the other waves' chunks land and the barrier opens.  Bit 1
+    // (rounds 6-9, off): pulled towards L2 into the wave's own (still unused) kilobyte and thrown away, whole groups only (that
+    // path has no bounds), the real request at the top of the walk.  Only the image is waited for.
     const int n_chunks = n_tiles * NCH;
     const unsigned img_at = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>(wimg));
     const unsigned lane16 = lane * 16;
@@ -461,16 +498,25 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
 #pragma unroll
         for (int q = 0; q < NQ; ++q) wl_dma16(gb, v_lane_off + (unsigned)t * 32u * (unsigned)ldv * 4u + 32u * q, lds_at);
       asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NT * NQ) : "memory");
+    } else if (ROWS_FIRST && wave < RAYEN_WL_EARLY && grp < n_groups) {
+      // (bit 2) the first rows of the workgroup's first RAYEN_WL_EARLY waves behind the image's chunks: NT * NQ loads --
+      // everything older has landed once that many are outstanding.  Every other wave waits for everything.
+      request(grp, std::true_type{});
+      asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NT * NQ) : "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
   }
 #endif
   if (RAYEN_WL_AHEAD && grp < n_groups) {
-    request(grp);
+    request(grp, std::false_type{});
     half_max();
   }
   __syncthreads();  // the only workgroup barrier: the image is in LDS
+  // (bit 2) the later waves' first rows, behind the barrier as in rounds 6-9: they arrive while the early waves split and multiply
+  if constexpr (ROWS_FIRST) {
+    if (wave >= RAYEN_WL_EARLY && grp < n_groups) request(grp, std::true_type{});
+  }
 
   while (grp < n_groups) {
     const int64_t s_base = grp * (NT * 32);
@@ -486,7 +532,8 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
       drain_at = next >= n_groups ? n_items / 3 : 0x7FFFFFFF;
     }
     if constexpr (!RAYEN_WL_AHEAD) {
-      request(grp);
+      // (ROWS_FIRST: the rows were requested in the head or at the bottom of the previous group; only their first use is here)
+      if constexpr (!ROWS_FIRST) request(grp, std::false_type{});
       half_max();
     }
 
@@ -623,7 +670,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- the next group's rows: in flight for the whole walk
-    if (RAYEN_WL_AHEAD && next < n_groups && !(RAYEN_WL_ABL & 1)) request(next);
+    if (RAYEN_WL_AHEAD && next < n_groups && !(RAYEN_WL_ABL & 1)) request(next, std::false_type{});
     __builtin_amdgcn_sched_barrier(0);
 
     // kap, part, the aux patch and the accumulators live in the SCALED domain (gW sv times the natural value)
@@ -801,8 +848,10 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
           if (sc_next.cnst > 0.f || sc_next.cabs > 0.f) {
             WlScreen s = sc_next;
             int nx = it + 1, ts_to = ts_next;
-            int ts_held = ts_next;      // the item whose operands abuf holds in full (-2: a probe has overwritten leading pieces)
-            auto kmax_now = [&] { return wl_half_max<SWAP>(kap[0]); };
+            const int ts_held = ts_next;      // the item whose operands abuf holds (the probe reads operands of its own)
+            // (kap does not change between here and the end of the decisions: the probe writes acc and part only)
+            [[maybe_unused]] const float kmax_held = wl_half_max<SWAP>(kap[0]);
+            auto kmax_now = [&] { return RAYEN_WL_KMAX_ONCE ? kmax_held : wl_half_max<SWAP>(kap[0]); };
             // (a NaN or an infinite row decides nothing: every comparison with it is false)
             const bool nv_ok = nv2 < __builtin_inff();
             // (the probe's margin is proved for a row whose largest scaled entry reached 2^13 -- every row but one below 2^-113,
@@ -830,16 +879,16 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
                 for (int j = 0; j < span; ++j) {
                   const char* tb = wimg + (size_t)(ts_j & 0xFFFFFF) * (NCH * 1024) + lane * 16;
                   const int shape = NS == 4 ? __builtin_amdgcn_readfirstlane((ts_j >> 24) & 3) : MS_FULL;
+                  // (operands of the probe's own, always from LDS -- the first item's leading pieces a second time: a conditional
+                  // overwrite of abuf cost ~30 register copies per probed segment, and a probe that fails finds abuf intact)
                   auto lead = [&](auto S0, auto S1) {
                     constexpr int s0 = decltype(S0)::value, s1 = decltype(S1)::value;
-                    if (ts_j != ts_held) {
+                    u32x4 pa[NS];
 #pragma unroll
-                      for (int sp = s0; sp < s1; ++sp) abuf[2 * sp] = *reinterpret_cast<const u32x4*>(tb + (2 * sp) * 1024);
-                      ts_held = -2;
-                    }
+                    for (int sp = s0; sp < s1; ++sp) pa[sp] = *reinterpret_cast<const u32x4*>(tb + (2 * sp) * 1024);
 #pragma unroll
                     for (int sp = s0; sp < s1; ++sp)
-                      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, abuf[2 * sp]), vb[0][0][sp],
+                      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, pa[sp]), vb[0][0][sp],
                                                                       sp == s0 ? zero : acc[0], 0, 0, 0);
                   };
                   if constexpr (NS == 4) {
@@ -885,7 +934,7 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
               ts_next = ts_to < 0 ? ts_first : ts_to;
               it = nx - 1;
             }
-            // (a probe that failed on a segment of several items, or ran behind a skipped segment, has overwritten leading pieces)
+            // (nothing skipped: abuf still holds the next item's operands, whatever the probes read)
             if (ts_held != ts_next) fetch(ts_next);
           }
         }
@@ -961,6 +1010,12 @@ __global__ __launch_bounds__(NW * 64, 1) void mfma_pair_wl_kernel(
     if (clock_groups == 0) RAYEN_WL_CLOCK_AT(2);
     ++clock_groups;
 #endif
+    // (ROWS_FIRST) the next group's rows, right behind the last store of y: the row registers are dead from the split to here, and
+    // the guard is the loop's own condition.  The wait at the top covers these stores either way (vmcnt retires in order).
+    if constexpr (ROWS_FIRST) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (next < n_groups) request(next, std::false_type{});
+    }
     grp = next;
   }  // persistent loop over sample groups
   if (nan_flag && bad) atomicOr(nan_flag, 1);
