@@ -275,10 +275,11 @@ __device__ __forceinline__ void reduce_column(T* A, int r, int kc, T* dd, T* ee,
   T* rd = red + (kc & 1) * 2 * kWaves;
   const T x = has ? A[Ti + kc] : T(0);
   if (has && part == 0) vv[i] = x;
-  const T sigma = bsum<T, NW>(part == 0 ? x * x : T(0), rd, tid);   // barrier 1 (vv = the raw column is visible too)
+  // what the reflector has to annihilate, summed without the sub-diagonal entry (sigma - x0^2 loses what is below sqrt(eps) |x0|)
+  const T below = bsum<T, NW>(part == 0 && i != i0 ? x * x : T(0), rd, tid);   // barrier 1 (vv = the raw column is visible too)
   LB_TICK(0);
   const T x0 = vv[i0];
-  const T below = sigma - x0 * x0;                               // what the reflector has to annihilate
+  const T sigma = fma(x0, x0, below);
   if (!(below > lw::Eps<T>::tiny * lw::Eps<T>::tiny)) {          // nothing to do: H = I  (the same for every thread)
     if (tid == 0) { dd[kc] = A[kc * (kc + 1) / 2 + kc]; ee[kc] = x0; if constexpr (KEEP) tt[kc] = T(0); }
     __syncthreads();
@@ -441,9 +442,9 @@ __device__ __forceinline__ void head_phase(T* A, int r, T (&head)[HC / 2], T* dd
         if (rw == 0 && c >= i0) ww[c * ncontrib + contributor] = val;
       }
     }
-    const T sigma = bsum<T, NW>(part == pk ? xown * xown : T(0), rd, tid);        // barrier 1
+    const T below = bsum<T, NW>(part == pk && i != i0 ? xown * xown : T(0), rd, tid);        // barrier 1 (rows >= kc + 2 alone)
     const T x0 = vv[i0];
-    const T below = sigma - x0 * x0;
+    const T sigma = fma(x0, x0, below);
     if (!(below > lw::Eps<T>::tiny * lw::Eps<T>::tiny)) {          // H = I
       if (tid == 0) { ee[kc] = x0; if constexpr (KEEP) tt[kc] = T(0); }
       __syncthreads();

@@ -99,13 +99,15 @@ __device__ __forceinline__ void tridiagonalise(T* A, const int LD, const int r, 
   for (int kc = 0; kc + 2 < r; ++kc) {
     const int i0 = kc + 1;
     const T x0 = A[i0 * LD + kc];
-    T sigma = T(0);
-    for (int i = i0 + lane; i < r; i += 64) {
+    // what the reflector has to annihilate, summed WITHOUT the sub-diagonal entry: in sigma - x0^2 every entry below
+    // sqrt(eps) |x0| is lost, and with it an eigenvalue's first order where the top pair nearly ties
+    T below = T(0);
+    for (int i = i0 + 1 + lane; i < r; i += 64) {
       const T xi = A[i * LD + kc];
-      sigma = fma(xi, xi, sigma);
+      below = fma(xi, xi, below);
     }
-    sigma = wsum(sigma);
-    const T below = sigma - x0 * x0;   // what the reflector has to annihilate
+    below = wsum(below);
+    const T sigma = fma(x0, x0, below);
     if (!(below > Eps<T>::tiny * Eps<T>::tiny)) {   // nothing to do: H = I
       if (lane == 0) { dd[kc] = A[kc * LD + kc]; ee[kc] = x0; tau[kc] = T(0); }
       for (int i = i0 + lane; i < r; i += 64) A[i * LD + kc] = T(0);
